@@ -12,6 +12,12 @@ ranks (--mode file, antiz_amd.shard): an all-gather of the scan results, a cost-
 streams, and a gather of the ATZ1 pieces to rank 0 over RCCL -- strong scaling.  --mode shards (every
 rank its own 1 GB file, seed 4 + rank: weak scaling) is a labelled secondary line.
 
+A plain run sets up, warms up, times --steps steps and prints the result line (the roofline and detail
+fields come from the timed steps' own statistics and cost no further run).  --dump-outputs DIR also
+writes what the last timed step returned, as DIR/<name>.npy (dump_outputs below).  Everything that takes
+runs of its own -- cpu_baseline, reconstruct, host_to_host and the atz_parity check of the timed run's
+ATZ1 against the reference's SHA-256 -- runs only with --full.
+
 roofline: the dominant kernel (k_trial_*: deflate trials) -- achieved = algorithmic bytes
 (trial input read + compare read, summed over the launches) / the kernels' summed
 device time (HIP events recorded inside libatz_accel on its own stream), peak = MI355X HBM 8 TB/s;
@@ -157,6 +163,43 @@ def pmc_issue():
     return out
 
 
+DUMP_SAMPLE = 8 * 1000 * 1000   # bytes of the ATZ1 sampled by --dump-outputs (float32: 32 MB)
+DUMP_BLOCK = 65536              # block size of the per-block byte sums, which cover every byte
+
+
+def dump_outputs(outdir, out, n, st):
+    """--dump-outputs: what the last timed step returned to its caller, as float .npy files.
+    `out` is the ATZ1 in HBM (a device pointer, or the tensor of the N > 1 file mode), `n` its length.
+      atz_len.npy         [n] (float64)
+      atz_sample.npy      the ATZ1's bytes (float32): all of them up to DUMP_SAMPLE bytes, else the bytes at
+                          DUMP_SAMPLE sorted positions drawn by a generator seeded with 0 (the same positions
+                          for the same n)
+      atz_block_sums.npy  the sum of every DUMP_BLOCK-byte block of the ATZ1 (float64, exact): every byte counts
+      counts.npy          file_bytes, n_streams, n_recomp, atz_bytes of the step's statistics (float64)"""
+    import numpy as np
+    import torch
+    if isinstance(out, int):
+        t = torch.empty(n, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        hip_copy(t.data_ptr(), out, n)
+    else:
+        t = out[:n]
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE))
+        sample = t[torch.from_numpy(idx).to(t.device)]
+    else:
+        sample = t
+    pad = (-n) % DUMP_BLOCK
+    blocks = torch.cat([t, torch.zeros(pad, dtype=torch.uint8, device=t.device)]) if pad else t
+    sums = blocks.view(-1, DUMP_BLOCK).sum(dim=1, dtype=torch.int64)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "atz_len.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(outdir, "atz_sample.npy"), sample.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(outdir, "atz_block_sums.npy"), sums.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(outdir, "counts.npy"),
+            np.array([st[k] for k in ("file_bytes", "n_streams", "n_recomp", "atz_bytes")], dtype=np.float64))
+
+
 def aggregate(dt, atz_len, shard_bytes, steps, world, device):
     """Cross-rank reduction of one timed run: max step time over ranks, per-rank ATZ sizes.
     value = bytes all ranks processed / the slowest rank's time (weak scaling: one shard per rank)."""
@@ -204,10 +247,15 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--streams", type=int, default=100000, help="streams per rank (C4: 100000 = 1 GB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: cpu_baseline, reconstruct, host_to_host "
+                         "and the atz_parity check against the reference's SHA-256 (each takes runs of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-sample-streams", type=int, default=8000)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-recon", action="store_true", help="skip the reconstruct (-r / verify) measurement")
-    ap.add_argument("--no-h2h", action="store_true", help="skip the host-to-host (atz_precompress) measurement")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline measurement")
+    ap.add_argument("--no-recon", action="store_true", help="with --full: skip the reconstruct (-r / verify) measurement")
+    ap.add_argument("--no-h2h", action="store_true", help="with --full: skip the host-to-host (atz_precompress) measurement")
     ap.add_argument("--cache", default=os.environ.get("ATZ_BENCH_CACHE", "/tmp/atz_bench_cache"))
     ap.add_argument("--workload", choices=("c4", "c5", "c4c3", "c2", "c3"), default="c4",
                     help="c4: the metric's workload (BASELINE configs[3]); c5: configs[4], the same generator with "
@@ -224,6 +272,8 @@ def main():
                          "rank 0; strong scaling); shards: every rank precompresses its own 1 GB file (weak scaling, "
                          "no data-path collective; a secondary line)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.mode == "file" and args.files_per_gpu > 1:
         ap.error("--files-per-gpu > 1 needs --mode shards (one file per step is split in file mode)")
 
@@ -267,9 +317,9 @@ def main():
         data = f.read()
     log("rank %d: workload %s (%.1f MB) ready in %.1fs" % (rank, os.path.basename(path), len(data) / 1e6, time.time() - t0))
     # input resident in HBM before the timed region (+4 KiB slack the kernels may over-read)
-    host = torch.frombuffer(bytearray(data) + bytearray(4096), dtype=torch.uint8)
-    dev = host.to("cuda", non_blocking=False)
+    dev = torch.zeros(len(data) + 4096, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
+    hip_copy(dev.data_ptr(), data, len(data))
 
     ctx = antiz_amd.Context(device=local, brute_window=args.workload == "c5")
     group = None
@@ -336,6 +386,10 @@ def main():
     ms_per_step = dt * 1000.0 / args.steps
 
     last = stats[-1]
+    if args.dump_outputs and rank == 0:
+        if last_out[0] is None:
+            raise RuntimeError("--dump-outputs needs --files-per-gpu 1")
+        dump_outputs(args.dump_outputs, last_out[0], n, last)
     ktime = last["k_trial_ms"] / 1000.0
     alg = last["k_trial_alg_bytes"]
     achieved = alg / ktime / 1e9 if ktime > 0 else 0.0
@@ -360,7 +414,7 @@ def main():
     # configs, tests/golden/share_configs.json for the per-rank share files (--streams 12500 / 25000 /
     # 50000) and the C4 + C3 cluster file
     atz_check = None
-    if rank == 0 and last_out[0] is not None and (args.mode == "file" or not extra):
+    if args.full and rank == 0 and last_out[0] is not None and (args.mode == "file" or not extra):
         gold = os.path.join(ROOT, "tests", "golden")
         sp = os.path.join(gold, "share_configs.json")
         ref = (json.load(open(sp)) if os.path.exists(sp) else {}).get("%s:%d" % (args.workload, args.streams))
@@ -384,7 +438,7 @@ def main():
     # resident in HBM; not part of the metric: its own wall time, and the round trip checked.  Every rank
     # of a shards run, and the one-GPU file run (at N > 1 in file mode the ATZ1 sits on rank 0 only)
     recon = None
-    if (args.mode == "shards" or world == 1) and not args.no_recon:
+    if args.full and (args.mode == "shards" or world == 1) and not args.no_recon:
         dptr, alen, _ = ctx.precompress_device(dev.data_ptr(), data)
         hdev = torch.empty(alen + 4096, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
@@ -409,7 +463,7 @@ def main():
 
     # the product path as the CLI runs it: host buffer in, host ATZ1 bytes out (H2D + D2H included)
     h2h = None
-    if world == 1 and not args.no_h2h:
+    if args.full and world == 1 and not args.no_h2h:
         import ctypes
         L = antiz_amd.lib()
         p, n, st = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64(0), antiz_amd.Stats()
@@ -424,7 +478,7 @@ def main():
         h2h = {"value": round(len(data) / 1e6 / ts[-1], 3), "unit": "MB/s", "ms": round(ts[-1] * 1000, 2),
                "atz_bytes": n.value, "what": "atz_precompress: host file bytes -> host ATZ1 bytes (H2D of the input, "
                                              "D2H of the ATZ1 included), the uncomp CLI's path; not the metric's value"}
-    elif world > 1 and args.mode == "file" and not args.no_h2h:
+    elif args.full and world > 1 and args.mode == "file" and not args.no_h2h:
         # the host path at N > 1 (antiz_amd.shard.precompress_sharded_to_file): every rank copies its own
         # piece from its HBM into the output file at its offset, rank 0 writes the header and the residue
         from antiz_amd import shard
@@ -451,7 +505,7 @@ def main():
             os.remove(opath)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(args.cpu_sample_streams, seed, ctx, args.workload)
 
     if rank == 0:

@@ -5,7 +5,8 @@
 # AB_WORKLOAD=c2|c3|c5: another BASELINE config (bench.py --workload)
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 TAG=$1; R=$2; shift 2
-mkdir -p gpurun_out/$TAG
+O=${ATZ_OUT:-bench_out}/$TAG   # ATZ_OUT: the directory the results go under
+mkdir -p $O
 timeout -k 10 300 python3 -c "
 import sys; sys.path.insert(0,'.')
 from antiz_amd import datagen
@@ -16,7 +17,7 @@ for ((i=1;i<=R;i++)); do
   for E in "$@"; do
     k=$((k+1))
     [ "$E" = "-" ] && E=""
-    env $E timeout -k 10 240 python3 bench.py --workload ${AB_WORKLOAD:-c4} --streams ${AB_STREAMS:-100000} --steps 3 --warmup 1 --no-cpu --no-recon --no-h2h > gpurun_out/$TAG/v$k.$i.json 2> gpurun_out/$TAG/v$k.$i.err || exit 1
-    echo "v$k.$i [$E] $(python3 -c "import json;d=json.load(open('gpurun_out/$TAG/v$k.$i.json'));print(d['value'],d['ms_per_step'],(d.get('atz_parity') or {}).get('identical_to_reference'),{x:d['detail'].get(x) for x in ('k_trial_ms','k_match_ms','k_chains_ms','k_inflate_ms','n_trials','n_trials_replayed','n_replay_checked','n_trials_duplicate','n_trials_speculative','n_trials_skipped')})")"
+    env $E timeout -k 10 240 python3 bench.py --workload ${AB_WORKLOAD:-c4} --streams ${AB_STREAMS:-100000} --steps 3 --warmup 1 --full --no-cpu --no-recon --no-h2h > $O/v$k.$i.json 2> $O/v$k.$i.err || exit 1
+    echo "v$k.$i [$E] $(python3 -c "import json;d=json.load(open('$O/v$k.$i.json'));print(d['value'],d['ms_per_step'],(d.get('atz_parity') or {}).get('identical_to_reference'),{x:d['detail'].get(x) for x in ('k_trial_ms','k_match_ms','k_chains_ms','k_inflate_ms','n_trials','n_trials_replayed','n_replay_checked','n_trials_duplicate','n_trials_speculative','n_trials_skipped')})")"
   done
 done

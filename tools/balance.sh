@@ -17,7 +17,7 @@ for wl in ${WLS:-c4 c4c3}; do
     echo "== $wl hint=$hint $(date +%T)"
     ATZ_SPLIT_HINT=$hint timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W \
       --master-addr 127.0.0.1 --master-port $port bench.py --gpus $W --steps 1 --warmup 1 --workload $wl \
-      --no-cpu > $out/${wl}_h$hint.json 2> $out/${wl}_h$hint.log || { echo "FAILED rc=$?"; tail -20 $out/${wl}_h$hint.log; exit 1; }
+      --full --no-cpu > $out/${wl}_h$hint.json 2> $out/${wl}_h$hint.log || { echo "FAILED rc=$?"; tail -20 $out/${wl}_h$hint.log; exit 1; }
     python3 -c "
 import json,sys
 d=json.loads(open('$out/${wl}_h$hint.json').read().strip().splitlines()[-1])

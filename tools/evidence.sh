@@ -18,7 +18,7 @@ case $P in
        ATZ_PIPES=6 GPU_MAX_HW_QUEUES=8 timeout -k 10 300 python3 bench.py --streams 12500 --steps 3 --warmup 1 --no-cpu --no-recon --no-h2h > $O/q8p6_s12500_$i.json 2> $O/q8p6_s12500_$i.err || exit 21
      done
      for w in c2 c3 c5; do
-       timeout -k 10 600 python3 bench.py --workload $w > $O/$w.json 2> $O/$w.err || exit 22
+       timeout -k 10 600 python3 bench.py --full --workload $w > $O/$w.json 2> $O/$w.err || exit 22
      done ;;
   d) WLS="c4 c4c3" HINTS=1 bash tools/balance.sh ${T}_bal 8 || exit 31 ;;
   e) for i in 1 2 3; do

@@ -28,24 +28,24 @@ if has knobs; then
 fi
 for W in c2 c3 c5; do
   if has $W; then
-    timeout -k 10 600 python3 bench.py --workload $W > $O/$W.json 2> $O/$W.err || exit 13
+    timeout -k 10 600 python3 bench.py --full --workload $W > $O/$W.json 2> $O/$W.err || exit 13
   fi
 done
 if has bench; then
-  timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || exit 3
+  timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 3
 fi
 if has timing; then
-  ATZ_TIMING=2 timeout -k 10 200 python3 bench.py --steps 1 --warmup 1 --no-cpu --no-recon > $O/timing.json 2> $O/timing.err || exit 7
+  ATZ_TIMING=2 timeout -k 10 200 python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-recon > $O/timing.json 2> $O/timing.err || exit 7
 fi
 if has small; then
-  ATZ_TIMING=2 timeout -k 10 200 python3 bench.py --streams 12500 --steps 2 --warmup 1 --no-cpu --no-recon > $O/small.json 2> $O/small.err || exit 8
+  ATZ_TIMING=2 timeout -k 10 200 python3 bench.py --full --streams 12500 --steps 2 --warmup 1 --no-cpu --no-recon > $O/small.json 2> $O/small.err || exit 8
 fi
 if has shardtest; then
   timeout -k 10 600 python3 -u -m pytest tests/test_gpu_shard.py -m gpu -x -v --timeout 300 --timeout-method thread > $O/shardtest.log 2>&1 || exit 9
 fi
 for N in 2 4 8; do
   if has file$N; then
-    ATZ_BENCH_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 2 --warmup 1 --no-recon > $O/file$N.json 2> $O/file$N.err || exit 10
+    ATZ_BENCH_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --full --steps 2 --warmup 1 --no-recon > $O/file$N.json 2> $O/file$N.err || exit 10
   fi
 done
 if has prof; then

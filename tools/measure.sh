@@ -22,7 +22,7 @@ if has gpu; then
   timeout -k 10 900 python3 -u -m pytest tests/test_gpu.py tests/test_gpu_knobs.py -m gpu -x -v --timeout 300 --timeout-method thread > $O/test.log 2>&1 || exit 2
 fi
 if has bench; then
-  timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || exit 3
+  timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 3
 fi
 if has timing; then
   ATZ_TIMING=2 timeout -k 10 200 python3 bench.py --steps 1 --warmup 1 --no-cpu --no-recon --no-h2h > $O/timing.json 2> $O/timing.err || exit 7
