@@ -136,9 +136,31 @@ def ora_precompress(data, chunksize=524288, recomp=128, sizediff=128, shortcut=5
     atz = C.string_at(p, n.value)
     L.ora_free(p)
     streams = [{k: getattr(res.streams[i], k) for k, _ in OraStream._fields_} for i in range(res.n_streams)]
+    for s in streams:   # the delta-encoded list (deltaEncode, main.cpp:757-763) as absolute positions in the stream
+        assert s["diff_index"] + s["n_diff"] <= res.n_diffs
+        at, s["diff_pos"] = s["first_diff"], []
+        for k in range(s["diff_index"], s["diff_index"] + s["n_diff"]):
+            at += res.diff_off[k]
+            s["diff_pos"].append(at)
+        s["diff_val"] = bytes(res.diff_val[k] for k in range(s["diff_index"], s["diff_index"] + s["n_diff"]))
     stats = dict(trials=res.n_trials, bailed=res.n_shortcut_bailed, hazard=res.n_hazard, streams=streams)
     L.ora_result_free(C.byref(res))
     return 0, atz, stats
+
+
+def diff_lists(results, diffs):
+    """Each stream's (absolute positions, values) from antiz_amd.Context.sweep()'s results and its
+    delta-encoded (diff_off, diff_val) arrays (include/atz_accel.h: diff_index, n_diff, first_diff)."""
+    offs, vals = diffs
+    out = []
+    for r in results:
+        assert r["diff_index"] + r["n_diff"] <= len(offs) == len(vals)
+        at, pos = r["first_diff"], []
+        for k in range(r["diff_index"], r["diff_index"] + r["n_diff"]):
+            at += offs[k]
+            pos.append(at)
+        out.append((pos, vals[r["diff_index"]:r["diff_index"] + r["n_diff"]]))
+    return out
 
 
 def ora_reconstruct(atz):

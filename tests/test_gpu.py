@@ -250,6 +250,12 @@ def test_scan_and_sweep_tables_match_oracle(atz):
         got = [(r["clevel"], r["window"], r["memlevel"], r["ident"], r["recomp"]) for r in res]
         exp = [(s["clevel"], s["window"], s["memlevel"], s["ident"], s["recomp"]) for s in st["streams"]]
         assert got == exp
+        # the diff lists (first_diff, n_diff, diff_index into diff_off / diff_val) of the recompressed streams
+        for r, s, (pos, val) in zip(res, st["streams"], _libs.diff_lists(res, diffs)):
+            assert (r["n_diff"], pos, val) == (s["n_diff"], s["diff_pos"], s["diff_val"]), s["offset"]
+            if s["n_diff"]:
+                assert r["first_diff"] == s["first_diff"]
+        assert len(diffs[0]) == sum(s["n_diff"] for s in st["streams"])
 
 
 def test_roundtrip_large_mixed(atz):
@@ -631,6 +637,12 @@ def test_speculative_scan_withdrawal(atz, monkeypatch):
         assert sha(out) == sha(ref) and st["n_continuations"] > 0
 
 
+# What oracle/ora_pipeline.c returns where the reference's behaviour is undefined: chunksize < 2 (-2), a
+# stream past EOF (-10), a re-inflate that fails (-11), the uint64 wrap in the residue copy (-20), an empty
+# input (-21).  Its other codes (-1, -12: allocation or deflate failures) are failures of the oracle itself.
+ORACLE_UB_CODES = (-2, -10, -11, -20, -21)
+
+
 @pytest.mark.parametrize("n,seed", [(160, 20261018), (800, 7)], ids=["pinned", "wide"])
 def test_fuzz_small_files_vs_oracle(atz, n, seed):
     """Seeded random small files (tests/golden_cases.py fuzz_cases) under chunk sizes from 2 bytes up
@@ -642,6 +654,7 @@ def test_fuzz_small_files_vs_oracle(atz, n, seed):
         rc, want, _ = _libs.ora_precompress(data, chunksize=cs, **G.opts_kwargs(opts))
         with atz.Context(chunksize=cs, **opts) as c:
             if rc != 0:   # the oracle's reference-UB codes (its own numbering): the library must fail too
+                assert rc in ORACLE_UB_CODES, (i, len(data), cs, opts, rc)   # any other failure is the oracle's own
                 with pytest.raises(atz.AtzError) as ei:
                     c.precompress(data)
                 assert ei.value.code == -6, (i, len(data), cs, opts)   # ATZ_E_REF_UB

@@ -4,15 +4,18 @@ These run without a GPU.  They establish that oracle/ reproduces zlib 1.2.8 defl
 (G2, from the reference's vendored zlib) and the reference pipeline's .atz bytes (G1 = the
 reference's own ZT vectors, G3-G5 = cases produced by the real reference binary).
 """
+import functools
 import hashlib
 import json
 import os
 import random
+from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
 import _libs
 import golden_cases as G
+import nearmiss as NM
 
 GOLD = G.GOLD
 
@@ -162,3 +165,118 @@ def test_fuzz_small_files_pin_the_oracle():
             assert f["rc"] != 0 and rc != 0, (i, cs, opts, f["rc"], rc)
         checked += 1
     assert checked >= 150
+
+
+# ---- near-miss streams (tests/nearmiss.py, tests/golden/nearmiss.json) ----------------------------------
+
+
+@functools.lru_cache(maxsize=None)
+def _nearmiss_default(name):
+    rc, atz, st = _libs.ora_precompress(NM.files()[name][0])
+    assert rc == 0
+    return atz, st
+
+
+@pytest.mark.parametrize("name", NM.NAMES)
+def test_nearmiss_fixture_pins_the_oracle(name):
+    """The oracle's ATZ1 on every near-miss file under every setting of tests/golden/nearmiss.json equals
+    the real reference's (tools/make_nearmiss_golden.py): SHA-256, length and the recompressed count; under
+    the default setting also the stream table (offset, comp_len, c, w, m, n_diff, first_diff of every
+    recompressed stream).  Every ATZ1 reconstructs its input."""
+    fx = NM.fixture()
+    data, _ = NM.files()[name]
+    NM.check_pinned(fx)
+    assert fx["settings"] == NM.settings(fx["T"], fx["D"])
+
+    def run(sname):
+        if sname == "default":
+            return _nearmiss_default(name)
+        rc, atz, st = _libs.ora_precompress(data, **NM.flags_kwargs(fx["settings"][sname]))
+        assert rc == 0
+        return atz, st
+
+    with ThreadPoolExecutor(8) as ex:     # the oracle runs outside the interpreter lock
+        runs = dict(zip(fx["settings"], ex.map(run, fx["settings"])))
+    for sname, flags in fx["settings"].items():
+        atz, st = runs[sname]
+        assert st["hazard"] == 0
+        rc, rec = _libs.ora_reconstruct(atz)
+        assert rc == 0 and rec == data, (name, sname)
+        table = [[e[k] for k in ("offset", "comp_len", "c", "w", "m", "n_diff", "first_diff")] for e in NM.parse_atz1(atz)]
+        mine = [[s["offset"], s["comp_len"], s["clevel"], s["window"], s["memlevel"], s["n_diff"],
+                 s["first_diff"] if s["n_diff"] else -1] for s in st["streams"] if s["recomp"]]
+        assert mine == table, (name, sname)       # the returned fields say what the ATZ1 says
+        e = fx["files"][name]["runs"][sname]
+        n_rec = sum(s["recomp"] for s in st["streams"])
+        assert (sha(atz), len(atz), "recompressed:%d/%d" % (n_rec, len(st["streams"]))) == \
+            (e["atz_sha256"], e["atz_bytes"], e["tail"]), (name, sname, flags)
+        if sname == "default":
+            assert table == fx["files"][name]["table"], name
+
+
+def test_nearmiss_diff_positions_are_the_generators():
+    """Independent of both implementations: the diff positions of a storedpad or mixed stream are exactly the
+    bytes whose padding bits the generator set (values: the original's bytes), k <= 128 of them are
+    recompressed and k > 128 are not; an eobpad stream's last diff is at C - 5, any other at offset 1 (the
+    re-levelled header); a tailflush stream's list runs to its last byte."""
+    seen = set()
+    for name, (data, streams) in NM.files().items():
+        _, st = _nearmiss_default(name)
+        by = {s["offset"]: s for s in st["streams"]}
+        for g in streams:
+            o = by[g.offset]
+            assert (o["comp_len"], o["infl_len"]) == (g.length, g.data_len), (name, g)
+            orig = data[g.offset:g.offset + g.length]
+            assert o["diff_val"] == bytes(orig[p] for p in o["diff_pos"])
+            assert o["n_diff"] == (g.length - o["ident"] if o["recomp"] else 0)
+            if g.family in ("storedpad", "mixed"):
+                k = len(g.pads)
+                assert g.length - o["ident"] == k and bool(o["recomp"]) == (k <= 128), (name, g)
+                if o["recomp"]:
+                    assert o["diff_pos"] == list(g.pads) and o["first_diff"] == g.pads[0], (name, g)
+                    seen.add(k)
+            elif g.family == "eobpad":
+                assert o["recomp"] and o["diff_pos"] in ([g.length - 5], [1, g.length - 5]), (name, g)
+            elif g.family == "tailflush":
+                assert o["recomp"] and o["diff_pos"][-1] == g.length - 1 and o["n_trials"] >= 81, (name, g)
+    assert seen == {k for k in NM.PAD_KS if k <= 128} | {5, 20}
+
+
+def test_nearmiss_tolerance_stop_decides():
+    """Independent of both implementations: a tolstop stream's first trial (level 5, memLevel 8) misses it
+    by d0 bytes and a later one is exact.  With mismatch_tol >= d0 the sweep stops there (main.cpp:700:
+    ident + tol >= C): level 5, d0 diffs, one trial; with mismatch_tol = d0 - 1 or less it goes on to a
+    better trial.  d0 sits at the default tolerance, at T and T - 1 (the fixture's settings) and one to
+    either side.  A wrongwin stream is recompressed only by the brute-window phase, with two diffs."""
+    fx = NM.fixture()
+    data, streams = NM.files()["tolstop"]
+    seen = set()
+    for sname, tol in (("default", 2), ("tol0", 0), ("tolT", fx["T"]), ("tolT-1", fx["T"] - 1)):
+        assert NM.flags_kwargs(fx["settings"][sname]).get("tol", 2) == tol
+        rc, _, st = _libs.ora_precompress(data, tol=tol)
+        assert rc == 0
+        by = {s["offset"]: s for s in st["streams"]}
+        for g in streams:
+            o, d0 = by[g.offset], int(g.tag[1:])
+            if d0 <= tol:
+                assert (o["clevel"], o["memlevel"], o["n_diff"], o["n_trials"]) == (5, 8, d0, 1), (sname, g)
+            else:
+                assert o["clevel"] < 5 and o["n_diff"] < d0 and o["n_trials"] > 1, (sname, g)
+                assert o["n_diff"] == 0 or o["n_diff"] <= tol, (sname, g)
+            seen.add((d0 - tol, d0 <= tol))
+    assert {(0, True), (1, False), (-1, True)} <= seen      # at the tolerance, one above it, one below it
+    data, streams = NM.files()["wrongwin"]
+    for brute in (0, 1):
+        rc, _, st = _libs.ora_precompress(data, brute=brute)
+        by = {s["offset"]: s for s in st["streams"]}
+        for g in streams:
+            o = by[g.offset]
+            assert (o["recomp"], o["diff_pos"]) == ((1, [0, 1]) if brute else (0, [])), (brute, g)
+            assert not brute or o["window"] == int(g.tag[1:3])
+
+
+def test_nearmiss_streams_inflate():
+    """zlib ignores a stored block's padding bits and the bits after the last end-of-block code
+    (Z/inflate.c: BYTEBITS()); so does the oracle's inflate on every mutated stream."""
+    for s, n in NM.mutated_streams():
+        assert _libs.ora_inflate(s + b"xy") == (0, len(s), n)
