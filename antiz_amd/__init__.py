@@ -54,7 +54,34 @@ class Stats(C.Structure):
 EXPORTS = ["atz_open", "atz_close", "atz_strerror", "atz_free", "atz_default_opts", "atz_scan", "atz_sweep",
            "atz_precompress", "atz_precompress_device", "atz_reconstruct", "atz_deflate", "atz_deflate_batch",
            "atz_inflate_batch", "atz_deflate_bound", "atz_shard_scan", "atz_shard_sweep", "atz_shard_piece",
-           "atz_shard_assemble", "atz_reconstruct_device"]
+           "atz_shard_assemble", "atz_reconstruct_device", "atz_deflate_batch_ex", "atz_set_strategies"]
+
+# zlib's strategy numbers (Z_FIXED, 4, is not supported); a strategy mask has bit k set for strategy k
+STRATEGIES = {"filtered": 1, "huffman": 2, "rle": 3}
+
+
+def strategy_mask(names):
+    """("filtered", "rle", ...) or a comma-separated string -> atz_set_strategies mask; ValueError on an unknown word."""
+    if isinstance(names, str):
+        names = [w for w in names.split(",") if w]
+    mask = 0
+    for w in names:
+        if w not in STRATEGIES:
+            raise ValueError("unknown strategy %r (known: %s)" % (w, ", ".join(sorted(STRATEGIES))))
+        mask |= 1 << STRATEGIES[w]
+    return mask
+
+
+def pack_clevel(strategy, level):
+    """The clevel byte of an ATZ2 descriptor (and of atz_sweep's results): strategy << 4 | level."""
+    if not (0 <= strategy <= 3 and 0 <= level <= 9) or (strategy >= 2 and level < 1):
+        raise ValueError("strategy %d with level %d" % (strategy, level))
+    return (strategy << 4) | level
+
+
+def unpack_clevel(b):
+    """-> (strategy, level) of a clevel byte."""
+    return b >> 4, b & 15
 
 _lib = None
 
@@ -94,6 +121,8 @@ def lib():
         L.atz_deflate_batch.argtypes = [C.c_void_p, C.c_char_p, u64, C.POINTER(u64), C.POINTER(u64),
                                         C.POINTER(C.c_uint32), u64, C.c_char_p, C.POINTER(u64), C.POINTER(u64),
                                         C.POINTER(u64)]
+        L.atz_deflate_batch_ex.argtypes = L.atz_deflate_batch.argtypes
+        L.atz_set_strategies.argtypes = [C.c_void_p, C.c_uint32]
         L.atz_deflate_bound.restype = u64
         L.atz_deflate_bound.argtypes = [u64, C.c_int, C.c_int]
         L.atz_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, u64, C.c_int, C.c_int, C.POINTER(u8p),
@@ -119,11 +148,19 @@ class Context:
     """One libatz_accel context (one GPU).  Mirrors the reference's programOptions (ATZData.h:7-35)."""
 
     def __init__(self, recomp_tresh=128, sizediff_tresh=128, shortcut_len=512, mismatch_tol=2,
-                 chunksize=524288, brute_window=False, device=-1):
+                 chunksize=524288, brute_window=False, device=-1, strategies=None):
+        """strategies: names of zlib strategies ("filtered", "rle", "huffman") to try on the streams the
+        reference walk leaves unrecorded (an extension, off by default; None reads ATZ_STRATEGIES, a
+        comma-separated list, as the CLI does)."""
         L = lib()
         self.o = Opts(recomp_tresh, sizediff_tresh, shortcut_len, mismatch_tol, chunksize, int(brute_window), device)
+        if strategies is None:
+            strategies = os.environ.get("ATZ_STRATEGIES", "")
+        mask = strategy_mask(strategies)
         self.h = C.c_void_p()
         _check(L.atz_open(C.byref(self.h), C.byref(self.o)))
+        if mask:
+            _check(L.atz_set_strategies(self.h, mask))
 
     def close(self):
         if self.h:
@@ -233,7 +270,9 @@ class Context:
         self._cands = None
         return out, diffs
 
-    def deflate(self, data, clevel, window, memlevel):
+    def deflate(self, data, clevel, window, memlevel, strategy=0):
+        if strategy:
+            return self.deflate_batch(data, [(0, len(data), clevel, window, memlevel, strategy)])[0]
         L = lib()
         cap = L.atz_deflate_bound(len(data), 10, 1) + 1024
         out = C.create_string_buffer(cap)
@@ -242,12 +281,14 @@ class Context:
         return out.raw[:n.value]
 
     def deflate_batch(self, buf, items):
-        """items: list of (offset, length, clevel, window, memlevel) over `buf`; returns list of bytes."""
+        """items: list of (offset, length, clevel, window, memlevel[, strategy]) over `buf`; returns list of bytes."""
         L = lib()
         k = len(items)
         offs = (u64 * max(k, 1))(*[it[0] for it in items])
         lens = (u64 * max(k, 1))(*[it[1] for it in items])
-        prm = (C.c_uint32 * max(k, 1))(*[(it[2] << 16) | (it[3] << 8) | it[4] for it in items])
+        ex = any(len(it) > 5 and it[5] for it in items)
+        prm = (C.c_uint32 * max(k, 1))(*[((it[5] << 24) if len(it) > 5 else 0) | (it[2] << 16) | (it[3] << 8) | it[4]
+                                         for it in items])
         caps = [L.atz_deflate_bound(it[1], 10, 1) + 64 for it in items]
         oo, tot = [], 0
         for cp in caps:
@@ -257,7 +298,8 @@ class Context:
         ooff = (u64 * max(k, 1))(*oo)
         ocap = (u64 * max(k, 1))(*caps)
         olen = (u64 * max(k, 1))()
-        _check(L.atz_deflate_batch(self.h, buf, len(buf), offs, lens, prm, k, out, ooff, ocap, olen))
+        fn = L.atz_deflate_batch_ex if ex else L.atz_deflate_batch
+        _check(fn(self.h, buf, len(buf), offs, lens, prm, k, out, ooff, ocap, olen))
         raw = out.raw
         return [raw[oo[i]:oo[i] + olen[i]] for i in range(k)]
 

@@ -663,6 +663,9 @@ struct atz_ctx {
   // atz_scan -> atz_sweep hand-off: set by a successful atz_scan, cleared by every call that
   // replaces recs / d_file (precompress, deflate, reconstruct, inflate_batch)
   bool scan_valid = false;
+  // opt-in strategy trials (atz_set_strategies): bit k = zlib strategy k (1 Z_FILTERED, 2 Z_HUFFMAN_ONLY,
+  // 3 Z_RLE) is tried on the streams the reference walk leaves unrecorded; 0: off
+  uint32_t strat_mask = 0;
   // atz_sweep reports every stream's best ident, c, w, m as the reference computes them; the precompress
   // paths only need what the ATZ1 holds, so they let trials stop once they cannot make their stream
   // recompressible (elig_floor)
@@ -1820,6 +1823,11 @@ static uint32_t mw_cap_for(size_t n_streams) {
   return v >= 0 ? (uint32_t)v : n_streams <= 16000 ? 4u : 2u;
 }
 static bool mw_trial(const Pipe* c, int kind, uint32_t memlevel) { return kind != 0 && memlevel <= c->mw_cap; }
+// the kernel a trial of kind k runs on: bit 0 multi-wave, bits 1-2 its strategy (Trial::mode bits 6-7:
+// 1 Z_FILTERED on the slow kind, 3 Z_RLE / 2 Z_HUFFMAN_ONLY on the table-less kind 0)
+static uint32_t trial_variant(const Pipe* c, int k, const Trial& t) {
+  return (mw_trial(c, k, t.memlevel) ? 1u : 0u) | ((uint32_t)(t.mode >> 6) << 1);
+}
 static uint64_t sym_words(const Pipe* c, int kind, uint32_t memlevel, uint64_t n) {   // symbol buffer of a trial (u32 units)
   return (mw_trial(c, kind, memlevel) ? n + 64 : 0) + (1ull << (memlevel + 6)) + 64;
 }
@@ -1843,8 +1851,10 @@ static void trials_order(atz_ctx* x, const Pipe* c, std::vector<Trial>* in, Tria
     std::vector<uint64_t> key(n);
     const uint32_t mwm = c->mw_cap;
     const bool packed = n < (1u << 20);
+    bool strat = false;   // strategy trials (mode bits 6-7) among them
     for (size_t q = 0; q < n; q++) {
       const Trial& t = in[k][q];
+      strat |= (t.mode >> 6) != 0;
       const uint64_t w = x->recs[t.stream].infl_len * (uint64_t)(k == 1 ? 3 : 1) * (uint64_t)(10 - t.memlevel) *
                          (uint64_t)((t.mode & 8) ? 1 : 4);   // replays skip the match walks
       const uint64_t mw = k != 0 && t.memlevel <= mwm;
@@ -1863,6 +1873,11 @@ static void trials_order(atz_ctx* x, const Pipe* c, std::vector<Trial>* in, Tria
         return ma != mb ? ma : key[a] > key[b];
       });
     }
+    // strategy trials run on kernels of their own: one run per (multi-wave, strategy), in the order above
+    if (strat)
+      std::stable_sort(S.perm[k].begin(), S.perm[k].end(), [&](uint32_t a, uint32_t b) {
+        return trial_variant(c, k, in[k][a]) < trial_variant(c, k, in[k][b]);
+      });
     S.tr[k].resize(n);
     for (size_t q = 0; q < n; q++) S.tr[k][q] = in[k][S.perm[k][q]];
     S.res[k].clear();
@@ -1880,8 +1895,11 @@ static int trials_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, const SweepO
     HIPCHK(pipe_copy(c, c->d_trials.as<Trial>() + base + i, h + i, (j - i) * sizeof(Trial), hipMemcpyHostToDevice));
     i = j;
   }
-  auto launch1 = [&](const Trial* hh, size_t n1, size_t b1, bool mw) -> int {
+  auto launch1 = [&](const Trial* hh, size_t n1, size_t b1, uint32_t variant) -> int {
     (void)hh;
+    const bool mw = variant & 1u;
+    const uint32_t strat = variant >> 1;
+    if (strat && !((k == 2 && strat == 1) || (k == 0 && strat >= 2))) return ATZ_E_INTERNAL;
     SweepArgs A;
     A.file = d_cmp; A.infl = INFL_BASE; A.chains = CHAIN_BASE;
     A.R = c->d_R.as<uint2>();
@@ -1891,21 +1909,26 @@ static int trials_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, const SweepO
     A.stopj = c->stopj_cur;
     dim3 g((uint32_t)n1), b(mw ? MW_THREADS : 64);
     kbeg(c, 0);
-    if (k == 0) hipLaunchKernelGGL(k_trial_stored, g, b, 0, c->st, A);
+    if (k == 0 && strat == 3) hipLaunchKernelGGL(k_trial_rle, g, b, 0, c->st, A);
+    else if (k == 0 && strat == 2) hipLaunchKernelGGL(k_trial_huff, g, b, 0, c->st, A);
+    else if (k == 2 && strat == 1 && mw) hipLaunchKernelGGL(k_trial_slow_filt_mw, g, b, 0, c->st, A);
+    else if (k == 2 && strat == 1) hipLaunchKernelGGL(k_trial_slow_filt, g, b, 0, c->st, A);
+    else if (k == 0) hipLaunchKernelGGL(k_trial_stored, g, b, 0, c->st, A);
     else if (k == 1 && mw) hipLaunchKernelGGL(k_trial_fast_mw<BITMAP_BITS>, g, b, 0, c->st, A);
     else if (k == 1) hipLaunchKernelGGL(k_trial_fast<BITMAP_BITS>, g, b, 0, c->st, A);
     else if (mw) hipLaunchKernelGGL(k_trial_slow_mw, g, b, 0, c->st, A);
     else hipLaunchKernelGGL(k_trial_slow, g, b, 0, c->st, A);
     kend(c);
-    KCHECK(k == 0 ? "k_trial_stored" : k == 1 ? "k_trial_fast" : "k_trial_slow");
+    KCHECK(strat == 3 ? "k_trial_rle" : strat == 2 ? "k_trial_huff" : strat == 1 ? "k_trial_slow_filt"
+           : k == 0 ? "k_trial_stored" : k == 1 ? "k_trial_fast" : "k_trial_slow");
     return 0;
   };
   size_t i = 0;
-  while (i < cnt) {   // runs of equal multi-wave-ness: trials_order made them contiguous
-    const bool mw = mw_trial(c, k, h[i].memlevel);
+  while (i < cnt) {   // runs of equal multi-wave-ness (and strategy): trials_order made them contiguous
+    const uint32_t v = trial_variant(c, k, h[i]);
     size_t j = i + 1;
-    while (j < cnt && mw_trial(c, k, h[j].memlevel) == mw) j++;
-    if (int r = launch1(h + i, j - i, base + i, mw)) return r;
+    while (j < cnt && trial_variant(c, k, h[j]) == v) j++;
+    if (int r = launch1(h + i, j - i, base + i, v)) return r;
     i = j;
   }
   return 0;
@@ -3123,6 +3146,202 @@ struct SweepGuard {
   ~SweepGuard() { if (R.running) sweep_close(c, R, true); }
 };
 
+// ---------------------------------------------------------------------------------------------
+// Opt-in strategy trials (atz_set_strategies).  The reference never sweeps zlib's
+// strategy, so a Z_FILTERED (libpng's default), Z_RLE or Z_HUFFMAN_ONLY stream ends its walk unrecorded.
+// After the reference walk, unchanged, the streams it left with recomp == 0 get a second walk under the
+// same rule (testDeflateParams and the stop rule, main.cpp:616-700, restarted with identBytes = 0) over
+// the candidates their header's FLEVEL allows -- zlib writes FLEVEL from level and strategy
+// (Z/deflate.c:738-750): 0 for strategy >= Z_HUFFMAN_ONLY, else by level -- at the header's window,
+// memLevels 8, 9, 7..1, levels descending within a memLevel.  Entries: (strategy<<24)|(c<<16)|(w<<8)|m.
+static void strategy_list(std::vector<uint32_t>& l, int type, uint32_t mask) {
+  const int w = 10 + type / 4;
+  static const int mo[9] = {8, 9, 7, 6, 5, 4, 3, 2, 1};
+  auto add = [&](uint32_t strat, int chi, int clo) {
+    if (!((mask >> strat) & 1u)) return;
+    for (int m : mo)
+      for (int cl = chi; cl >= clo; cl--) l.push_back((strat << 24) | pk(cl, w, m));
+  };
+  switch (type % 4) {
+    case 0: add(3, 6, 6); add(2, 6, 6); break;   // the parse ignores the level: recorded as 6
+    case 1: add(1, 5, 4); break;                 // (levels 1-3 ignore Z_FILTERED: the default list's)
+    case 2: add(1, 6, 6); break;
+    default: add(1, 9, 7); break;
+  }
+}
+
+// One round per list position on pipe 0, the streams of a round in batches within the scratch budget (each
+// batch builds the bucket tables its filtered trials read, as deflate_dev does).  A stream the pass
+// records gets clevel = strategy << 4 | level; the others keep what the reference walk left.
+static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
+  if (!c->strat_mask) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t n = ss.size();
+  struct Ext {
+    std::vector<uint32_t> list;
+    uint32_t best = 0;
+    uint64_t ident = 0;
+    bool done = false;
+    std::vector<uint32_t> rawdiff;
+    std::vector<uint8_t> diffval;
+  };
+  std::vector<Ext> ex(n);
+  std::vector<uint32_t> todo;
+  size_t longest = 0;
+  for (size_t s = 0; s < n; s++) {
+    if (ss[s].recomp || c->recs[s].infl_len >= (1ull << 31)) continue;
+    strategy_list(ex[s].list, c->recs[s].type, c->strat_mask);
+    if (ex[s].list.empty()) continue;
+    todo.push_back((uint32_t)s);
+    longest = std::max(longest, ex[s].list.size());
+  }
+  if (todo.empty()) return 0;
+  if (int r = ensure_pipes(c, 1)) return r;
+  HIPCHK(hipStreamSynchronize(c->st));
+  Pipe* p = c->pipes[0].get();
+  c->pipes_running = 1;
+  p->mw_cap = mw_cap_for(todo.size());
+  p->stopj_cur = nullptr;
+  const atz_stats_t before = p->stats;
+  const SweepOpts so{c->o.recomp_tresh, c->o.sizediff_tresh, c->o.shortcut_len, c->o.mismatch_tol};
+  const uint64_t budget = cap_bytes(ROUND_BUDGET_BYTES);
+  for (auto& a : c->chain_off) a.fill(~0ull);
+  uint64_t ntr = 0, nsc = 0, nhz = 0;
+  for (size_t j = 0; j < longest; j++) {
+    std::vector<uint32_t> act;
+    for (uint32_t s : todo)
+      if (!ex[s].done && j < ex[s].list.size()) act.push_back(s);
+    if (act.empty()) break;
+    for (size_t a0 = 0; a0 < act.size();) {
+      size_t a1 = a0;
+      uint64_t bytes = 0;
+      while (a1 < act.size() && (a1 == a0 || bytes <= budget)) {
+        const uint32_t s = act[a1], q = ex[s].list[j];
+        const uint64_t len = c->recs[s].infl_len;
+        bytes += 9 * len + 4 * sym_words(p, 2, q & 0xff, len) + bound(len, (int)((q >> 8) & 0xff), (int)(q & 0xff)) + 4096;
+        a1++;
+      }
+      for (size_t a = a0; a < a1; a++) c->chain_off[act[a]].fill(~0ull);
+      c->chain_arena.reset(cap_bytes(CHAIN_CACHE_CAP));   // the last batch's kernels are done (run_trials synchronised)
+      p->tmp_chains.clear();
+      p->chains_next = 0;
+      std::vector<std::pair<uint32_t, int>> need;
+      for (size_t a = a0; a < a1; a++) {
+        const uint32_t q = ex[act[a]].list[j];
+        if ((q >> 24) == 1) need.push_back({act[a], (int)(q & 0xff)});
+      }
+      if (int r = ensure_chains(c, p, need)) return r;
+      HIPCHK(hipStreamSynchronize(p->st));
+      std::vector<Trial> tr[3];
+      std::vector<uint32_t> who[3];
+      uint64_t out_tot = 0, sym_tot = 0;
+      for (size_t a = a0; a < a1; a++) {
+        const uint32_t s = act[a], q = ex[s].list[j];
+        const uint32_t strat = q >> 24;
+        const int cl = (int)((q >> 16) & 0xff), w = (int)((q >> 8) & 0xff), m = (int)(q & 0xff);
+        const uint64_t len = c->recs[s].infl_len;
+        Trial t{};
+        t.stream = s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)m;
+        t.mode = (uint8_t)(strat << 6);   // never saves, replays or stands for a duplicate
+        t.best_ident = std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len));
+        t.out_off = out_tot; t.out_cap = bound(len, w, m) + 64;
+        out_tot += (t.out_cap + 255) & ~255ull;
+        const int kind = strat == 1 ? 2 : 0;
+        t.sym_off = sym_tot; sym_tot += sym_words(p, kind, (uint32_t)m, len);
+        if (kind) t.chain_off = c->chain_off[s][m];
+        tr[kind].push_back(t);
+        who[kind].push_back(s);
+      }
+      if (int r = p->d_out.reserve(out_tot + 4096)) return r;
+      if (int r = p->d_syms.reserve(sym_tot * 4 + 4096)) return r;
+      std::vector<TrialRes> rr[3];
+      if (int r = run_trials(c, p, d_file, tr, so, rr)) return r;
+      // the rule (main.cpp:685-700) on each stream's trial; mismatch lists (main.cpp:699-714) of the
+      // improvements within recomp_tresh from the outputs, which the next batch overwrites
+      std::vector<DiffJob> dj;
+      std::vector<uint32_t> djs;
+      uint64_t dpos = 0;
+      for (int k = 0; k < 3; k += 2)
+        for (size_t q = 0; q < tr[k].size(); q++) {
+          const Trial& t = tr[k][q];
+          const TrialRes& r = rr[k][q];
+          const uint32_t s = who[k][q];
+          const uint64_t C = c->recs[s].comp_len;
+          Ext& e = ex[s];
+          if (r.state == TR_NEED_R || r.state == TR_SKIPPED) return ATZ_E_INTERNAL;
+          if (r.state == TR_OVERFLOW) return ATZ_E_REF_ABORT;   // deflate() without Z_STREAM_END, main.cpp:663-665
+          ss[s].trials++;
+          ntr++;
+          nsc += r.state == TR_SHORTCUT;
+          nhz += r.flags & 1;
+          if (r.state != TR_FULL || r.ident <= e.ident) continue;
+          e.ident = r.ident;
+          e.best = e.list[j];
+          e.rawdiff.clear(); e.diffval.clear();
+          if (r.ident == C || r.ident + c->o.mismatch_tol >= C) e.done = true;
+          if (r.ident != C && C - r.ident <= c->o.recomp_tresh) {
+            DiffJob d{};
+            d.out_off = t.out_off; d.out_len = r.out_len; d.orig_off = c->recs[s].offset;
+            d.comp_len = C; d.dst = dpos; d.cap = C - r.ident;
+            dpos += d.cap;
+            dj.push_back(d);
+            djs.push_back(s);
+          }
+        }
+      if (!dj.empty()) {
+        if (int r = upload(p, p->d_diffjobs, dj.data(), dj.size() * sizeof(DiffJob))) return r;
+        if (int r = p->d_diffpos.reserve(dpos * 4 + 64)) return r;
+        if (int r = p->d_diffval.reserve(dpos + 64)) return r;
+        if (int r = p->d_diffcnt.reserve(dj.size() * 8 + 64)) return r;
+        kbeg(p, 3);
+        hipLaunchKernelGGL(k_diffs, dim3((uint32_t)dj.size()), dim3(64), 0, p->st, p->d_out.as<uint8_t>(), d_file,
+                           p->d_diffjobs.as<DiffJob>(), p->d_diffpos.as<uint32_t>(), p->d_diffval.as<uint8_t>(),
+                           p->d_diffcnt.as<uint64_t>(), (uint32_t)dj.size());
+        kend(p);
+        std::vector<uint32_t> pos(dpos);
+        std::vector<uint8_t> val(dpos);
+        std::vector<uint64_t> cnt(dj.size());
+        HIPCHK(pipe_copy(p, pos.data(), p->d_diffpos.p, dpos * 4, hipMemcpyDeviceToHost));
+        HIPCHK(pipe_copy(p, val.data(), p->d_diffval.p, dpos, hipMemcpyDeviceToHost));
+        HIPCHK(pipe_copy(p, cnt.data(), p->d_diffcnt.p, dj.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHK(pipe_sync(p));
+        kcollect(p);
+        for (size_t q = 0; q < dj.size(); q++) {
+          if (cnt[q] != dj[q].cap) return ATZ_E_INTERNAL;
+          Ext& e = ex[djs[q]];
+          e.rawdiff.assign(pos.begin() + dj[q].dst, pos.begin() + dj[q].dst + dj[q].cap);
+          e.diffval.assign(val.begin() + dj[q].dst, val.begin() + dj[q].dst + dj[q].cap);
+        }
+      }
+      a0 = a1;
+    }
+  }
+  forget_tmp_chains(c, p);
+  for (uint32_t s : todo) {
+    Ext& e = ex[s];
+    const uint64_t C = c->recs[s].comp_len;
+    if (!(e.ident > 0 && C - e.ident <= c->o.recomp_tresh)) continue;   // main.cpp:454
+    StreamState& st = ss[s];
+    st.c = (uint8_t)(((e.best >> 24) << 4) | ((e.best >> 16) & 0xff));
+    st.w = (uint8_t)((e.best >> 8) & 0xff); st.m = (uint8_t)(e.best & 0xff);
+    st.ident = e.ident;
+    st.rawdiff.swap(e.rawdiff); st.diffval.swap(e.diffval);
+    st.first_diff = st.rawdiff.empty() ? -1 : (int64_t)st.rawdiff[0];
+    st.recomp = true;
+  }
+  atz_stats_t& t = c->stats;
+  const atz_stats_t& q = p->stats;
+  t.n_trials += ntr; t.n_trials_shortcut += nsc; t.n_hazard += nhz;
+  t.k_trial_ms += q.k_trial_ms - before.k_trial_ms; t.k_trial_launches += q.k_trial_launches - before.k_trial_launches;
+  t.k_chains_ms += q.k_chains_ms - before.k_chains_ms; t.k_chains_launches += q.k_chains_launches - before.k_chains_launches;
+  t.k_match_ms += q.k_match_ms - before.k_match_ms; t.k_match_launches += q.k_match_launches - before.k_match_launches;
+  t.k_other_ms += q.k_other_ms - before.k_other_ms;
+  t.sweep_ms += ms_since(t0);
+  if (timing_on()) std::fprintf(stderr, "atz: strategy pass: %zu streams, %llu trials  %9.2f ms\n", todo.size(),
+                                (unsigned long long)ntr, ms_since(t0));
+  return 0;
+}
+
 // the sweep of every record of the context (atz_sweep)
 static int sweep_impl(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
   const size_t n = c->recs.size();
@@ -3130,7 +3349,8 @@ static int sweep_impl(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState
   SweepGuard guard{c, R};
   if (int r = sweep_begin(c, d_file, ss, n, R)) return r;
   if (int r = sweep_publish(c, R, 0, n)) return r;
-  return sweep_finish(c, R);
+  if (int r = sweep_finish(c, R)) return r;
+  return strategy_pass(c, d_file, ss);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3200,8 +3420,9 @@ static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<
   return 0;
 }
 
-static void atz_header(std::vector<uint8_t>& meta, uint64_t F, uint64_t nrec) {
-  const uint8_t h[4] = {'A', 'T', 'Z', 1};
+// version 2 (the strategy extension): some descriptor's clevel byte is strategy << 4 | level
+static void atz_header(std::vector<uint8_t>& meta, uint64_t F, uint64_t nrec, uint8_t version = 1) {
+  const uint8_t h[4] = {'A', 'T', 'Z', version};
   meta.insert(meta.end(), h, h + 4);
   put8(meta, 0); put8(meta, F); put8(meta, nrec);   // length back-patched (main.cpp:776, 797-800)
 }
@@ -3213,8 +3434,12 @@ static int write_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::
   std::vector<Seg> segs;
   const size_t n = c->recs.size();
   uint64_t nrec = 0;
-  for (size_t s = 0; s < n; s++) nrec += ss[s].recomp;
-  atz_header(meta, F, nrec);
+  uint8_t version = 1;   // ATZ1 unless a recorded stream carries a strategy
+  for (size_t s = 0; s < n; s++) {
+    nrec += ss[s].recomp;
+    if (ss[s].recomp && (ss[s].c >> 4)) version = 2;
+  }
+  atz_header(meta, F, nrec, version);
   segs.push_back({0, 0, 0, 0, meta.size()});
   uint64_t out = meta.size();
   meta.reserve(meta.size() + nrec * 43 + 64);
@@ -3353,6 +3578,7 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   }
   c->stats.scan_ms = scan_busy;   // the scan thread's own time (the sweep runs beside it)
   if (int r = sweep_finish(c, R)) return r;
+  if (int r = strategy_pass(c, d_file, ss)) return r;
   c->infl_off.resize(c->recs.size());
   c->adler.resize(c->recs.size());
   if (int r = write_impl(c, d_file, F, ss, atz_len)) return r;
@@ -3415,19 +3641,24 @@ static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std:
     p->tmp_chains.clear();
     p->chains_next = 0;
     std::vector<std::pair<uint32_t, int>> need;
-    for (size_t s = s0; s < s1; s++) if ((params[s] >> 16) > 0) need.push_back({(uint32_t)s, (int)(params[s] & 0xff)});
+    // (params carry a strategy in bits 24-25: Z_RLE and Z_HUFFMAN_ONLY read no bucket tables)
+    for (size_t s = s0; s < s1; s++)
+      if (((params[s] >> 16) & 0xff) > 0 && (params[s] >> 24) < 2) need.push_back({(uint32_t)s, (int)(params[s] & 0xff)});
     if (int r = ensure_chains(c, p, need)) return r;
     HIPCHK(hipStreamSynchronize(p->st));
     std::vector<Trial> tr[3];
     std::vector<uint32_t> idx[3];
     uint64_t out_tot = 0, sym_tot = 0;
     for (size_t s = s0; s < s1; s++) {
-      const int cl = (int)(params[s] >> 16), w = (int)((params[s] >> 8) & 0xff), m = (int)(params[s] & 0xff);
+      const int cl = (int)((params[s] >> 16) & 0xff), w = (int)((params[s] >> 8) & 0xff), m = (int)(params[s] & 0xff);
+      // Z_FILTERED only changes deflate_slow (levels 4-9); Z_RLE / Z_HUFFMAN_ONLY replace the level's parse
+      const uint32_t sg = params[s] >> 24, strat = sg == 1 && cl < 4 ? 0u : sg;
       Trial t{};
-      t.stream = (uint32_t)s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)m; t.mode = 1;
+      t.stream = (uint32_t)s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)m;
+      t.mode = (uint8_t)(1u | (strat << 6));
       t.best_ident = 0; t.out_off = out_tot; t.out_cap = bound(len[s], w, m) + 64;
       out_tot += (t.out_cap + 255) & ~255ull;
-      const int kind = cl == 0 ? 0 : cl <= 3 ? 1 : 2;
+      const int kind = cl == 0 || strat >= 2 ? 0 : cl <= 3 ? 1 : 2;
       t.sym_off = sym_tot; sym_tot += sym_words(p, kind, (uint32_t)m, len[s]);
       if (kind) t.chain_off = c->chain_off[s][m];
       tr[kind].push_back(t);
@@ -3497,7 +3728,9 @@ struct AtzDesc { uint64_t off, cl, il, nd, fd, dpos, ipos; uint8_t c, w, m; };
 // ATZ1 parse with the reference's checks (main.cpp:1011-1063); every size field is bounded by the
 // bytes actually left before anything is sized from it (subtraction-only checks: no sum can wrap)
 static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, uint64_t& origlen, uint64_t& residue) {
-  if (n < 28 || std::memcmp(atz, "ATZ\1", 4) != 0) return ATZ_E_FORMAT;   // main.cpp:1018-1021
+  // version 2: the strategy extension's files (same layout; clevel = strategy << 4 | level)
+  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || (atz[3] != 1 && atz[3] != 2)) return ATZ_E_FORMAT;   // main.cpp:1018-1021
+  const bool v2 = atz[3] == 2;
   if (rd8(atz + 4) != n) return ATZ_E_FORMAT;                              // main.cpp:1022-1025
   origlen = rd8(atz + 12);
   const uint64_t nstrms = rd8(atz + 20);
@@ -3528,7 +3761,10 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
       x.fd = 0; x.dpos = 0; x.ipos = lastos + 35;
       lastos = x.ipos + x.il;
     }
-    if (x.c > 9 || x.w < 8 || x.w > 15 || x.m < 1 || x.m > 9) return ATZ_E_REF_ABORT;
+    if (v2) {   // Z_HUFFMAN_ONLY and Z_RLE have no level 0
+      if ((x.c & 15) > 9 || (x.c >> 4) > 3 || ((x.c >> 4) >= 2 && (x.c & 15) < 1)) return ATZ_E_REF_ABORT;
+    } else if (x.c > 9) return ATZ_E_REF_ABORT;
+    if (x.w < 8 || x.w > 15 || x.m < 1 || x.m > 9) return ATZ_E_REF_ABORT;
   }
   // streams in file order, inside the original (the writer emits them so; a crafted file with
   // overlapping or out-of-range streams is rejected before any buffer is sized)
@@ -3586,7 +3822,7 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
       addr[j] = (uint64_t)(uintptr_t)slab.p + loc[j];
       len[j] = d[j].il;
       const int w = d[j].w == 8 ? 9 : d[j].w;
-      params[j] = ((uint32_t)d[j].c << 16) | ((uint32_t)w << 8) | d[j].m;
+      params[j] = ((uint32_t)(d[j].c >> 4) << 24) | ((uint32_t)(d[j].c & 15) << 16) | ((uint32_t)w << 8) | d[j].m;
     }
     if (!segs.empty())
       if (int r = gather_segments(c, d_atz, meta, segs, slab.as<uint8_t>())) return r;
@@ -4142,9 +4378,10 @@ int atz_deflate(atz_ctx_t* c, const uint8_t* in, uint64_t in_len, int clevel, in
   });
 }
 
-int atz_deflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
-                      const uint32_t* params, uint64_t n, uint8_t* out, const uint64_t* out_offs,
-                      const uint64_t* out_caps, uint64_t* out_lens) {
+// ex: params carry zlib's strategy in bits 24-31 (atz_deflate_batch_ex); else bits 16-31 are the level
+static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
+                             const uint32_t* params, uint64_t n, uint8_t* out, const uint64_t* out_offs,
+                             const uint64_t* out_caps, uint64_t* out_lens, bool ex) {
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || (!buf && len) || !out_lens) return ATZ_E_ARG;
@@ -4152,11 +4389,13 @@ int atz_deflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint
     std::vector<uint32_t> ps(n);
     for (uint64_t k = 0; k < n; k++) {
       if (offs[k] + lens[k] > len) return ATZ_E_ARG;
-      int cl = (int)(params[k] >> 16), w = (int)((params[k] >> 8) & 0xff), m = (int)(params[k] & 0xff);
+      const int sg = ex ? (int)(params[k] >> 24) : 0;
+      int cl = (int)(ex ? (params[k] >> 16) & 0xff : params[k] >> 16), w = (int)((params[k] >> 8) & 0xff), m = (int)(params[k] & 0xff);
       if (cl < 0 || cl > 9 || w < 8 || w > 15 || m < 1 || m > 9) return ATZ_E_ARG;
+      if (sg > 3 || (sg >= 2 && cl < 1)) return ATZ_E_ARG;   // Z_FIXED is not supported; Z_RLE / Z_HUFFMAN_ONLY have no level 0
       if (w == 8) w = 9;
       ins[k] = {buf + offs[k], lens[k]};
-      ps[k] = ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
+      ps[k] = ((uint32_t)sg << 24) | ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
     }
     std::vector<std::vector<uint8_t>> outs;
     if (int r = deflate_many(c, ins, ps, outs)) return r;
@@ -4167,6 +4406,24 @@ int atz_deflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint
     }
     return ATZ_OK;
   });
+}
+
+int atz_deflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
+                      const uint32_t* params, uint64_t n, uint8_t* out, const uint64_t* out_offs,
+                      const uint64_t* out_caps, uint64_t* out_lens) {
+  return deflate_batch_api(c, buf, len, offs, lens, params, n, out, out_offs, out_caps, out_lens, false);
+}
+
+int atz_deflate_batch_ex(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
+                         const uint32_t* params, uint64_t n, uint8_t* out, const uint64_t* out_offs,
+                         const uint64_t* out_caps, uint64_t* out_lens) {
+  return deflate_batch_api(c, buf, len, offs, lens, params, n, out, out_offs, out_caps, out_lens, true);
+}
+
+int atz_set_strategies(atz_ctx_t* c, uint32_t mask) {
+  if (!c || (mask & ~14u)) return ATZ_E_ARG;   // bits 1..3: Z_FILTERED, Z_HUFFMAN_ONLY, Z_RLE
+  c->strat_mask = mask;
+  return ATZ_OK;
 }
 
 int atz_inflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
@@ -4195,6 +4452,7 @@ int atz_shard_scan(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, u
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !blob || !blob_len || world < 1 || rank < 0 || rank >= world) return ATZ_E_ARG;
+    if (c->strat_mask) return ATZ_E_ARG;   // the strategy extension has no multi-GPU split
     dev_mark_call();   // (the peak runs on through atz_shard_sweep, whose stats report it)
     std::vector<uint64_t> b;
     if (int r = shard_scan_impl(c, d_file, h_file, len, rank, world, b)) { c->shard.stage = 0; return r; }
@@ -4212,6 +4470,7 @@ int atz_shard_sweep(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, 
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !piece_len || !recomp_flags || !n_flags || !n_recomp) return ATZ_E_ARG;
+    if (c->strat_mask) return ATZ_E_ARG;
     std::vector<uint8_t> f;
     if (int r = shard_sweep_impl(c, d_file, h_file, len, blobs, blob_lens, world, f, n_recomp)) {
       c->shard.stage = 0;

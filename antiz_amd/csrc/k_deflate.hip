@@ -1975,9 +1975,13 @@ static constexpr uint32_t TR_DECIDED = 0xfffffffeu;   // parser-side: a flusher 
 // over the match tables -- deflate_stored, a replay of a saved symbol sequence, deflate_fast or
 // deflate_slow -- with its blocks flushed as they fill, then the trailer and the final gates.  The
 // parse state lives in the members (registers, once everything is inlined).
-template <int KIND, typename SH>
+// KIND: 0 deflate_stored, 1 deflate_fast, 2 deflate_slow, 3 deflate_rle, 4 deflate_huff (the last two take
+// no chains and no match table).  STRAT: 1 = deflate_slow under Z_FILTERED (Trial::mode bits 6-7 carry
+// zlib's strategy number: the host picks the instantiation by it).
+template <int KIND, typename SH, int STRAT = 0>
 struct TrialRun {
   static constexpr bool MW = HasMW<SH>::value;
+  static constexpr bool TAB = KIND == 1 || KIND == 2;   // the parse reads chains and a match table
   const SweepArgs& A;
   SH& shm;
   const int lane, wave;
@@ -2026,7 +2030,7 @@ struct TrialRun {
       : A(A_), shm(shm_), lane(lane_), wave(MW ? (int)(threadIdx.x >> 6) : 0), s(*(LDS TrialShared*)&shm_.t),
         stg((LDS uint32_t*)shm_.ring), b(s.b), t(blockIdx.x), tr(A_.trials[t]), sd(A_.streams[tr.stream]),
         in(A_.infl + sd.infl_off), npad((uint32_t)((sd.infl_len + 63) & ~63ull)),
-        sidx(KIND == 0 ? nullptr : A_.chains + tr.chain_off), bpos(KIND == 0 ? nullptr : sidx + npad),
+        sidx(!TAB ? nullptr : A_.chains + tr.chain_off), bpos(!TAB ? nullptr : sidx + npad),
         full_needed(tr.mode & 1), lt(lane_ ? (~0ull >> (64 - lane_)) : 0ull) {
     z.level = tr.clevel; z.kind = KIND;
     z.wsize = 1u << tr.window; z.maxdist = z.wsize - LOOKMIN; z.lbs = 1u << (tr.memlevel + 6);
@@ -2042,8 +2046,8 @@ struct TrialRun {
     }
     // fast and slow levels: a saving trial writes its whole symbol sequence at rp_syms (block k's
     // symbols at sbase, the count of symbols in the blocks before it); a replaying trial reads one
-    saving = KIND != 0 && (tr.mode & 4);
-    replay = KIND != 0 && (tr.mode & 8);
+    saving = TAB && (tr.mode & 4);
+    replay = TAB && (tr.mode & 8);
     if (KIND == 2 && replay && (tr.mode & 16)) {
       const uint32_t tlim = tr.x_lim < sd.infl_len ? (uint32_t)tr.x_lim : (uint32_t)sd.infl_len;   // entries present
       // replay only if this trial's table agrees with the saver's on every entry the saver's parse
@@ -2086,7 +2090,7 @@ struct TrialRun {
     // zlib header (Z/deflate.c:738-759)
     if (wave == 0) {
       uint32_t header = (8u + ((uint32_t)(tr.window - 8) << 4)) << 8;
-      uint32_t lf = z.level < 2 ? 0 : z.level < 6 ? 1 : z.level == 6 ? 2 : 3;
+      uint32_t lf = z.level < 2 || KIND >= 3 ? 0 : z.level < 6 ? 1 : z.level == 6 ? 2 : 3;   // strategy >= Z_HUFFMAN_ONLY: 0
       header |= lf << 6;
       header += 31 - (header % 31);
       put_bits(b, stg, ((header >> 8) & 0xff) | ((header & 0xff) << 8), 16, lane);   // < 32 bits: no staging
@@ -2139,7 +2143,7 @@ struct TrialRun {
       sbase += z.last_lit;
       z.last_lit = 0;
       z.block_start = z.p;
-      if (KIND != 0 && !replay) {   // the tree scratch overlaid the ring: reload its resident chunks
+      if (TAB && !replay) {   // the tree scratch overlaid the ring: reload its resident chunks
         for (uint32_t c0 = hi >= RING_SLOW ? hi - RING_SLOW : 0u; c0 < hi; c0 += 64) {
           const uint32_t pos = c0 + (uint32_t)lane;
           if (pos < n) ring[pos & (RING_SLOW - 1)] = Rt[pos];
@@ -2169,7 +2173,7 @@ struct TrialRun {
     // uniform: the walks skip them with a scalar branch)
     noslide = ATZ_NOSLIDE_PATH && n <= wsz + maxd;
     // ring: chunks of 64 entries below `hi` are resident; the chunk at `hi` is in flight in pf
-    if (KIND != 0 && n && !replay) pf = Rt[lane];
+    if (TAB && n && !replay) pf = Rt[lane];
   }
 
   // deflate_stored (Z/deflate.c:1564-1619)
@@ -2712,7 +2716,9 @@ struct TrialRun {
           const uint32_t len = ex >> 23, dist = (ex >> 8) & 0x7fffu;
           if (hv && len > w_len) w_len = len;
           uint32_t ML = hv && len > 2 ? len : 2u;
-          if (ML == 3 && dist > 4096) ML = 2;   // TOO_FAR
+          // TOO_FAR; Z_FILTERED drops every match of length <= 5 (Z/deflate.c:1774-1782), which also keeps
+          // prev_length >= 6, so a lazy read of length <= 5 never improves it
+          if (STRAT == 1 ? ML <= 5 : (ML == 3 && dist > 4096)) ML = 2;
           if (ML == 2) { wt = 1; nxt = x + 1; break; }
           PL = ML; PD = dist; qq++;
           continue;
@@ -2819,6 +2825,155 @@ struct TrialRun {
     }
     z.p = n;
     z.S = S_iter(Sb, n);
+  }
+  }
+
+  // Window slides of deflate_rle: fill_window runs at the top of an iteration at q when lookahead <=
+  // MAX_MATCH (Z/deflate.c:1875), i.e. q >= S + 2 wsize - 258 while input is left to read, or n - q <= 258
+  // once it is exhausted, and slides when strstart - S >= wsize + MAX_DIST.  A match never jumps over the
+  // last 258 positions of the window, so S at an iteration is a function of its position.
+  __device__ __forceinline__ uint32_t S_rle(uint32_t S0, uint32_t q) const {
+      uint32_t Sx = S0;
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const bool exh = n <= Sx + 2u * wsz;
+        const bool slide = exh ? (q + 258u >= n && q >= Sx + wsz + maxd) : (q + 258u >= Sx + 2u * wsz);
+        if (slide) Sx += wsz;
+      }
+      return Sx;
+  }
+
+  __device__ __forceinline__ void parse_rle() {
+  // deflate_rle (Z/deflate.c:1861-1929), lane-parallel.  Every iteration starts in the same state, so the
+  // step at a position depends on the position alone: at x > 0 with three bytes left, a match of distance
+  // 1 if in[x-1] == in[x] == in[x+1] == in[x+2], as long as the run of in[x-1] from x (at most 258, and
+  // the bytes left); else a literal.  A window takes the steps of its 64 positions in lanes, the scalar
+  // unit follows the path, and the path's symbols are tallied in position order.
+  uint32_t q = 0, Sb = 0;
+  while (q < n) {
+    const uint32_t wb = q;
+    Sb = S_rle(Sb, wb);
+    const uint32_t x = wb + (uint32_t)lane;
+    // E[j]: positions wb + 64 j + lane equal to their predecessor; a later chunk is read only when a run
+    // can reach it (6 chunks: lane 63's run ends before wb + 63 + 258)
+    uint64_t E[6];
+    uint32_t b0 = 0;
+    bool more = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      E[j] = 0;
+      if (more) {
+        const uint32_t y = x + 64u * (uint32_t)j;
+        bool e = false;
+        if (y < n) {
+          const uint32_t by = in[y];
+          if (j == 0) b0 = by;
+          e = y > 0 && by == in[y - 1];
+        }
+        E[j] = __ballot(e);
+        more = j == 0 ? (E[0] >> 63) != 0 : E[j] == ~0ull;
+      }
+    }
+    uint32_t run = 0;   // positions from x on that equal in[x-1]
+    {
+      const uint64_t z0 = ~E[0] >> lane;
+      if (z0) run = (uint32_t)__builtin_ctzll(z0);
+      else {
+        run = 64u - (uint32_t)lane;
+#pragma unroll
+        for (int j = 1; j < 6; j++) {
+          const uint64_t zj = ~E[j];
+          if (zj) { run += (uint32_t)__builtin_ctzll(zj); break; }
+          run += 64u;
+        }
+      }
+    }
+    uint32_t wt = 0, L = 0;
+    if (x < n) {
+      wt = 1;
+      if (x > 0 && x + 3u <= n && run >= 3u) { wt = 2; L = run < 258u ? run : 258u; }   // run <= n - x
+    }
+    const uint64_t Am = __ballot(wt == 1);
+    const uint32_t rel = wt == 1 ? run_end_rel(Am, lane) : wt == 2 ? (uint32_t)lane + L : 0xffffu;
+    const WinPath wp = follow_path(rel, 0ull, n - wb < 64 ? n - wb : 64u);
+    bool onp;
+    uint32_t mab_unused;
+    path_lane(wp, Am, 0, lane, onp, mab_unused);
+    const uint64_t P = __ballot(onp);
+    const uint32_t o = (uint32_t)__popcll(P & lt);
+    const uint32_t T = (uint32_t)__popcll(P);
+    z.nsym += T;
+    uint32_t base = 0;
+    while (base < T) {
+      const uint32_t room = z.lbs - 1u - z.last_lit;
+      const uint32_t seg_end = T - base < room ? T : base + room;
+      if (onp && o >= base && o < seg_end) {
+        uint32_t v;
+        if (wt == 2) {
+          v = (1u << 8) | (L - 3u);
+          const uint32_t lc = 257u + len_code(L - 3u);
+          __hip_atomic_fetch_add(&s.f.lfreq2[lc >> 1], 1u << (16 * (lc & 1u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(&s.f.dfreq2[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // d_code(0) == 0
+        } else {
+          v = b0;
+          __hip_atomic_fetch_add(&s.f.lfreq2[v >> 1], 1u << (16 * (v & 1u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        syms[z.last_lit + (o - base)] = v;
+      }
+      z.last_lit += seg_end - base;
+      if (z.last_lit == z.lbs - 1u) {   // flush after the node tallied last: strstart past its step
+        const uint64_t om = __ballot(onp && o == seg_end - 1u);
+        const int ol = (int)__builtin_ctzll(om);
+        const uint32_t fx = (uint32_t)__builtin_amdgcn_readlane((int)x, ol);
+        const uint32_t fl = (uint32_t)__builtin_amdgcn_readlane((int)L, ol);
+        z.p = fx + (fl ? fl : 1u);
+        z.S = S_rle(Sb, fx);
+        state = FLUSH0();
+        if (state != ~0u) break;
+      }
+      base = seg_end;
+    }
+    if (state != ~0u) break;
+    q = wb + wp.end;
+  }
+  if (state == ~0u) {
+    z.p = n;
+    z.S = S_rle(Sb, n);   // the last iteration (lookahead 0) calls fill_window once more
+  }
+  }
+
+  __device__ __forceinline__ void parse_huff() {
+  // deflate_huff (Z/deflate.c:1934-1968): every byte a literal, 64 per step.  fill_window runs only when
+  // the lookahead is used up (position F): it slides when strstart - S >= wsize + MAX_DIST and reads up to
+  // the end of the 2 wsize window.
+  uint32_t q = 0, S = 0, F = 0;
+  for (;;) {
+    if (q == F) {
+      if (q - S >= wsz + maxd) S += wsz;
+      F = n - S < 2u * wsz ? n : S + 2u * wsz;
+      if (F == q) break;
+    }
+    const uint32_t room = z.lbs - 1u - z.last_lit;
+    uint32_t cnt = F - q < 64u ? F - q : 64u;
+    if (cnt > room) cnt = room;
+    if ((uint32_t)lane < cnt) {
+      const uint32_t v = in[q + (uint32_t)lane];
+      __hip_atomic_fetch_add(&s.f.lfreq2[v >> 1], 1u << (16 * (v & 1u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      syms[z.last_lit + (uint32_t)lane] = v;
+    }
+    z.last_lit += cnt;
+    z.nsym += cnt;
+    q += cnt;
+    if (z.last_lit == z.lbs - 1u) {
+      z.p = q;
+      z.S = S;
+      state = FLUSH0();
+      if (state != ~0u) break;
+    }
+  }
+  if (state == ~0u) {
+    z.p = n;
+    z.S = S;
   }
   }
 
@@ -2939,14 +3094,16 @@ struct TrialRun {
       if constexpr (KIND == 0) parse_stored();
       else if (replay) parse_replay();
       else if constexpr (KIND == 1) parse_fast();
-      else parse_slow();
+      else if constexpr (KIND == 2) parse_slow();
+      else if constexpr (KIND == 3) parse_rle();
+      else parse_huff();
       end_parse();
     }
     finish();
   }
 };
 
-template <int KIND, typename SH>
+template <int KIND, typename SH, int STRAT = 0>
 __device__ void trial_body(const SweepArgs& A, SH& shm, int lane) {
   if constexpr (!HasMW<SH>::value) {
     // a single-wave trial whose stream an earlier trial of the round has stopped ends before any set-up
@@ -2963,7 +3120,7 @@ __device__ void trial_body(const SweepArgs& A, SH& shm, int lane) {
       return;
     }
   }
-  TrialRun<KIND, SH> run(A, shm, lane);
+  TrialRun<KIND, SH, STRAT> run(A, shm, lane);
   run.run();
 }
 
@@ -2994,6 +3151,25 @@ __global__ __launch_bounds__(MW_THREADS, TRIAL_SLOW_WAVES) void k_trial_fast_mw(
 __global__ __launch_bounds__(MW_THREADS, TRIAL_SLOW_WAVES) void k_trial_slow_mw(SweepArgs A) {
   __shared__ TrialSharedSlowMW shm;
   trial_body<2>(A, shm, (int)(threadIdx.x & 63));
+}
+// Strategy trials (Trial::mode bits 6-7; opt-in): deflate_slow under Z_FILTERED on the
+// default strategy's chains and match tables, and deflate_rle / deflate_huff, which need neither (the ring
+// only holds the tree scratch and the emission staging)
+__global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_slow_filt(SweepArgs A) {
+  __shared__ TrialSharedSlow shm;
+  trial_body<2, TrialSharedSlow, 1>(A, shm, threadIdx.x);
+}
+__global__ __launch_bounds__(MW_THREADS, TRIAL_SLOW_WAVES) void k_trial_slow_filt_mw(SweepArgs A) {
+  __shared__ TrialSharedSlowMW shm;
+  trial_body<2, TrialSharedSlowMW, 1>(A, shm, (int)(threadIdx.x & 63));
+}
+__global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_rle(SweepArgs A) {
+  __shared__ TrialSharedSlow shm;
+  trial_body<3>(A, shm, threadIdx.x);
+}
+__global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_huff(SweepArgs A) {
+  __shared__ TrialSharedSlow shm;
+  trial_body<4>(A, shm, threadIdx.x);
 }
 
 }  // namespace atz

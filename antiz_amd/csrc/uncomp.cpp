@@ -397,7 +397,8 @@ int main(int argc, char* argv[]) {
       std::cout << "Cannot open file: " << a << std::endl;
       return -1;
     }
-    if (az.size() < 4 || std::memcmp(az.data(), "ATZ\1", 4) != 0) {
+    // ("ATZ\2": a file of the strategy extension, ATZ_STRATEGIES below; same layout)
+    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || (az[3] != 1 && az[3] != 2)) {
       std::cout << "Invalid file: ATZ1 header not found" << std::endl;
       return -2;
     }
@@ -432,7 +433,25 @@ int main(int argc, char* argv[]) {
     std::cerr << "Error Encountered: " << "failed to open File " << in << std::endl;
     return done(1);
   }
+  // ATZ_STRATEGIES=filtered,rle,huffman (any subset; not a reference flag): zlib strategies to try on the
+  // streams the reference's walk leaves unrecorded (atz_set_strategies)
+  uint32_t strategies = 0;
+  if (const char* e = std::getenv("ATZ_STRATEGIES")) {
+    std::stringstream words(e);
+    std::string w;
+    while (std::getline(words, w, ',')) {
+      if (w.empty()) continue;
+      if (w == "filtered") strategies |= 1u << 1;
+      else if (w == "huffman") strategies |= 1u << 2;
+      else if (w == "rle") strategies |= 1u << 3;
+      else {
+        std::cerr << "Error Encountered: " << "ATZ_STRATEGIES: unknown strategy " << w << std::endl;
+        return done(1);
+      }
+    }
+  }
   if (open_ctx()) return done(255);
+  if (strategies && atz_set_strategies(ctx, strategies) != 0) return done(255);
   uint8_t* atz = nullptr;
   uint64_t al = 0;
   atz_stats_t st;

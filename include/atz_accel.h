@@ -148,6 +148,22 @@ int atz_deflate_batch(atz_ctx_t *ctx, const uint8_t *buf, uint64_t len, const ui
                       const uint32_t *params, uint64_t n, uint8_t *out, const uint64_t *out_offs,
                       const uint64_t *out_caps, uint64_t *out_lens);
 
+/* atz_deflate_batch with zlib's strategy: params[i] = (strategy<<24)|(clevel<<16)|(window<<8)|memlevel,
+ * strategy 0 default, 1 Z_FILTERED, 2 Z_HUFFMAN_ONLY, 3 Z_RLE (zlib's numbering; Z_FIXED is not supported).
+ * Levels 0..9 for strategies 0-1 (levels 0-3 ignore Z_FILTERED, as zlib does), 1..9 for strategies 2-3. */
+int atz_deflate_batch_ex(atz_ctx_t *ctx, const uint8_t *buf, uint64_t len, const uint64_t *offs, const uint64_t *lens,
+                         const uint32_t *params, uint64_t n, uint8_t *out, const uint64_t *out_offs,
+                         const uint64_t *out_caps, uint64_t *out_lens);
+
+/* Opt-in strategy trials (an extension: the reference never sweeps the strategy).  mask bit k (k = 1..3)
+ * names zlib strategy k; 0, the default, is off and leaves every output as the reference's.  With a mask,
+ * the precompress and sweep calls give each stream the reference walk leaves unrecorded a second walk,
+ * under the same rule, over the masked strategies that its header's FLEVEL allows.  A stream recorded so
+ * reports clevel = strategy<<4 | level, and a file that holds one is written with the magic "ATZ\2" (same
+ * layout; the reference cannot read it), else the file is the ATZ1 of a context without a mask.
+ * atz_reconstruct* read both.  The atz_shard_* calls return ATZ_E_ARG on a context with a mask. */
+int atz_set_strategies(atz_ctx_t *ctx, uint32_t mask);
+
 /* Batch of independent one-shot inflates of the given ranges of a host buffer (parity/debug):
  * status[i] in {0 end, 1 error, 2 need input}, consumed[i] = zlib total_in, produced[i] = total_out. */
 int atz_inflate_batch(atz_ctx_t *ctx, const uint8_t *buf, uint64_t len, const uint64_t *offs,
