@@ -24,6 +24,26 @@ uint64_t ora_deflate_bound(uint64_t n, int wbits, int memlevel);
 int ora_deflate(const uint8_t *in, uint64_t n, int level, int wbits, int memlevel,
                 uint8_t *out, uint64_t out_cap, uint64_t *out_len, int *flags);
 
+/* Path counters of ora_deflate since the last reset (single-threaded use): how often _tr_flush_block and
+ * gen_bitlen took their rare branches.  A group of three is indexed by tree: +0 literal/length,
+ * +1 distance, +2 code-length. */
+enum {
+    ORA_CNT_FIXUP = 0,        /* [3] gen_bitlen's length-limit fix-up entered (Z/trees.c:531) */
+    ORA_CNT_FIXUP_MULTI = 3,  /* [3] ... with overflow > 2 on entry (the loop runs more than once) */
+    ORA_CNT_FIXUP_ODD = 6,    /* [3] ... with odd overflow on entry (it ends at -1) */
+    ORA_CNT_FIXUP_L_SMALL = 9,   /* literal/length fix-up with heap_len <= 63 after the forced codes */
+    ORA_CNT_FIXUP_L_LARGE = 10,  /* ... with heap_len > 63 */
+    ORA_CNT_STORED = 11, ORA_CNT_STATIC = 12, ORA_CNT_DYNAMIC = 13,   /* blocks emitted, by type */
+    ORA_CNT_TIE_STATIC = 14,  /* static_lenb == opt_lenb (level > 0) */
+    ORA_CNT_TIE_STORED = 15,  /* stored_len + 4 == opt_lenb (level > 0, block start still in the window) */
+    ORA_CNT_FORCED = 16,      /* [3] trees with fewer than two codes (Z/trees.c:645-653) */
+    ORA_CNT_MAXLEN = 19,      /* [3] dynamic blocks emitted with a code of max_length bits (15, 15, 7) */
+    ORA_CNT_N = 22
+};
+void ora_deflate_counters_reset(void);
+/* copies min(n, ORA_CNT_N) counters to out; returns ORA_CNT_N */
+int ora_deflate_counters(uint64_t *out, int n);
+
 /* ---- inflate (zlib 1.2.8 inflate.c / inffast.c / inftrees.c semantics) ---- */
 enum { ORA_INF_END = 0, ORA_INF_ERROR = 1, ORA_INF_NEED_INPUT = 2 };
 /* Decode a zlib stream from in[0..n).  out may be NULL (lengths only).

@@ -119,7 +119,10 @@ static int search_chunk(searcher *z, const uint8_t *buf, uint64_t len, svec *out
 int ora_scan(const uint8_t *file, uint64_t n, uint64_t cs, ora_result_t *res) {
     memset(res, 0, sizeof(*res));
     if (cs < 2) return -2;              /* reference loops forever at cs==1 (main.cpp:410-415) */
-    if (n == 0) return -21;             /* -21 is the oracle's own code: the reference reads rBuffer[-1] (main.cpp:406) and dies of SIGSEGV (the -11 in tests/golden/fuzz_small.json is that signal, not an oracle code); the library reports ATZ_E_REF_UB */
+    /* Empty input: the reference reads rBuffer[-1] (main.cpp:406) and dies of SIGSEGV (the -11 in
+     * tests/golden/fuzz_small.json is that signal, not an oracle code).  -21 is the oracle's own code for it;
+     * the library's is ATZ_E_REF_UB = -6. */
+    if (n == 0) return -21;
     svec out = {0};
     searcher z;
     memset(&z, 0, sizeof(z));

@@ -46,6 +46,8 @@ def ora():
                                   C.POINTER(u64), C.POINTER(C.c_int)]
         L.ora_deflate_bound.restype = u64
         L.ora_deflate_bound.argtypes = [u64, C.c_int, C.c_int]
+        L.ora_deflate_counters_reset.restype = None
+        L.ora_deflate_counters.argtypes = [C.POINTER(u64), C.c_int]
         L.ora_inflate.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.POINTER(u64), C.POINTER(u64)]
         L.ora_scan.argtypes = [C.c_char_p, u64, u64, C.POINTER(OraResult)]
         L.ora_sweep.argtypes = [C.c_char_p, u64, C.POINTER(OraOpts), C.POINTER(OraResult)]
@@ -90,6 +92,24 @@ def ora_deflate(data, c, w, m):
     r = L.ora_deflate(data, len(data), c, w, m, out, cap, C.byref(n), C.byref(fl))
     assert r == 0, r
     return out.raw[:n.value], fl.value
+
+
+# oracle/atz_oracle.h ORA_CNT_*; a name ending in _l, _d, _bl is per tree (literal/length, distance, code-length)
+ORA_COUNTERS = ("fixup_l", "fixup_d", "fixup_bl", "fixup_multi_l", "fixup_multi_d", "fixup_multi_bl",
+                "fixup_odd_l", "fixup_odd_d", "fixup_odd_bl", "fixup_l_small", "fixup_l_large",
+                "stored", "static", "dynamic", "tie_static", "tie_stored", "forced_l", "forced_d", "forced_bl",
+                "maxlen_l", "maxlen_d", "maxlen_bl")
+
+
+def ora_counters_reset():
+    ora().ora_deflate_counters_reset()
+
+
+def ora_counters():
+    """ora_deflate's path counters since the last reset, by name (the oracle is single-threaded here)."""
+    a = (u64 * len(ORA_COUNTERS))()
+    assert ora().ora_deflate_counters(a, len(a)) == len(a)
+    return dict(zip(ORA_COUNTERS, a))
 
 
 def zref_deflate(data, c, w, m):

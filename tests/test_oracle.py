@@ -14,8 +14,10 @@ from concurrent.futures import ThreadPoolExecutor
 import pytest
 
 import _libs
+import deeptrees as DT
 import golden_cases as G
 import nearmiss as NM
+import zstrat
 
 GOLD = G.GOLD
 
@@ -280,3 +282,91 @@ def test_nearmiss_streams_inflate():
     (Z/inflate.c: BYTEBITS()); so does the oracle's inflate on every mutated stream."""
     for s, n in NM.mutated_streams():
         assert _libs.ora_inflate(s + b"xy") == (0, len(s), n)
+
+
+# ---- trees deeper than the length limit (tests/deeptrees.py, tests/golden/deeptrees.json) ------------------
+
+
+@functools.lru_cache(maxsize=None)
+def _deeptrees_default():
+    return DT.run_counted(DT.default_items())
+
+
+def test_deeptrees_fixture_pins_the_oracle():
+    """The oracle's stream for every default-strategy item equals the real zlib 1.2.8's (length and SHA-256 in
+    tests/golden/deeptrees.json, make_deeptrees.py), and its inflate gives zlib's (status, consumed, produced) on
+    every stream and on the stream cut 1, 2, 5 and 9 bytes short -- the Z_RLE and Z_HUFFMAN_ONLY streams too,
+    where the reference's zlib is there to make them."""
+    fx = DT.fixture()
+    assert set(fx["items"]) == {it.name for it in DT.items()} and tuple(fx["cuts"]) == DT.CUTS
+    streams = dict(zip((it.name for it in DT.default_items()), _deeptrees_default()[0]))
+    if os.path.exists(zstrat.Z128_SO):
+        streams.update((it.name, DT.reference_stream(it)) for it in DT.items() if it.strategy)
+    assert len(streams) >= len(DT.default_items()) >= 90
+    for name, s in streams.items():
+        e = fx["items"][name]
+        assert [len(s), sha(s)] == e["deflate"], name
+        assert len(e["inflate"]) == len(DT.cuts_of(s)) >= 4
+        for (cut, part), want in zip(DT.cuts_of(s), e["inflate"]):
+            assert _libs.ora_inflate(part) == tuple(want), (name, cut)
+
+
+def test_deeptrees_reach_the_fixup():
+    """What the inputs are for, counted by the oracle (atz_oracle.h ORA_CNT_*) over the default-strategy items:
+    gen_bitlen's length-limit fix-up (Z/trees.c:531-564) on each of the three trees, with more than one turn
+    of its loop (overflow > 2), on literal/length trees of more than 63 leaves and of at most 63 (k_deflate's
+    LDS heap and register heap); both block-type ties; trees with forced codes; and streams that carry a
+    15-bit literal/length code, a 15-bit distance code and a 7-bit code-length code.  The counts are the
+    fixture's "_reach".
+
+    overflow is never odd: gen_bitlen counts every node whose depth exceeds max_length, leaf or not
+    (Z/trees.c:512-515 increments before the leaf test), a Huffman tree's nodes below the root come in sibling
+    pairs of one depth, so the count is even and the loop ends at 0, never at -1.  The counter stays, at 0."""
+    c = _deeptrees_default()[1]
+    print("reach:", c)
+    assert c == DT.fixture()["_reach"]
+    assert c["fixup_bl"] >= 20 and c["fixup_multi_bl"] >= 5
+    assert c["fixup_d"] >= 2 and c["fixup_multi_d"] >= 1
+    assert c["fixup_l_large"] >= 4 and c["fixup_l_small"] >= 1
+    assert c["fixup_l"] == c["fixup_l_large"] + c["fixup_l_small"] and c["fixup_multi_l"] >= 1
+    assert c["fixup_odd_l"] + c["fixup_odd_d"] + c["fixup_odd_bl"] == 0
+    assert c["tie_static"] >= 1 and c["tie_stored"] >= 1
+    assert c["forced_l"] >= 1 and c["forced_d"] >= 1
+    assert c["stored"] >= 1 and c["static"] >= 1 and c["dynamic"] >= 100
+    assert c["maxlen_l"] >= 1 and c["maxlen_d"] >= 1 and c["maxlen_bl"] >= 1
+
+
+def test_deeptrees_counters_leave_the_output_alone():
+    """Reset and read between runs: the same bytes, and one run's counts add up."""
+    it = next(i for i in DT.default_items() if i.name.startswith("l_deep_large"))
+    a, ca = DT.run_counted([it])
+    b, cb = DT.run_counted([it, it])
+    assert a[0] == b[0] == b[1] and ca["fixup_l_large"] >= 1
+    assert all(cb[k] == 2 * ca[k] for k in ca)
+    assert ca["stored"] + ca["static"] + ca["dynamic"] >= 1
+
+
+def test_deeptrees_huffman_only_blocks_are_deep():
+    """Family huff_fib needs no search: under Z_HUFFMAN_ONLY a block's literal histogram is its bytes' (plus
+    the end-of-block symbol), so the depth of its unlimited Huffman tree is computed here, not assumed:
+    above 15 for the first block of every item, at least 19 for k = 20, with at most 63 leaves (the register
+    heap) for the plain items and more for the ones over flat byte values (the LDS heap); the block after a
+    deep one, where there is one, is shallow."""
+    deep = DT.deep_block_items()
+    assert len(deep) >= 12
+    leaves = set()
+    for it, blk, k in deep:
+        assert it.strategy == DT.Z_HUFFMAN_ONLY
+        hists = DT.literal_blocks(it.data, it.memlevel)
+        depth = DT.huffman_depth(hists[blk])
+        assert depth > 15 and (k < 20 or "flat" in it.name or depth >= 19), (it.name, depth)
+        n = sum(1 for f in hists[blk] if f)
+        assert (n > 63) == ("flat" in it.name or "then_text_m8" in it.name), (it.name, n)
+        leaves.add(n > 63)
+        if "then_text" in it.name:
+            assert len(hists) == 2 and DT.huffman_depth(hists[1]) <= 15, it.name
+        else:
+            assert len(it.data) <= (1 << (it.memlevel + 6)) - 1, it.name
+    assert leaves == {False, True}
+    assert DT.huffman_depth(DT.fib_counts(16)) == 15     # the end-of-block symbol's 1 is the chain's last link
+    assert [DT.huffman_depth(DT.chain_counts(k)) for k in (17, 18)] == [16, 17]
