@@ -1823,14 +1823,41 @@ static uint32_t mw_cap_for(size_t n_streams) {
   return v >= 0 ? (uint32_t)v : n_streams <= 16000 ? 4u : 2u;
 }
 static bool mw_trial(const Pipe* c, int kind, uint32_t memlevel) { return kind != 0 && memlevel <= c->mw_cap; }
-// the kernel a trial of kind k runs on: bit 0 multi-wave, bits 1-2 its strategy (Trial::mode bits 6-7:
+// the kernel a trial of kind k runs on: bit 0 multi-wave, bits 1-2 its strategy (Trial::host & TH_STRAT:
 // 1 Z_FILTERED on the slow kind, 3 Z_RLE / 2 Z_HUFFMAN_ONLY on the table-less kind 0)
 static uint32_t trial_variant(const Pipe* c, int k, const Trial& t) {
-  return (mw_trial(c, k, t.memlevel) ? 1u : 0u) | ((uint32_t)(t.mode >> 6) << 1);
+  return (mw_trial(c, k, t.memlevel) ? 1u : 0u) | ((t.host & TH_STRAT) << 1);
 }
 static uint64_t sym_words(const Pipe* c, int kind, uint32_t memlevel, uint64_t n) {   // symbol buffer of a trial (u32 units)
   return (mw_trial(c, kind, memlevel) ? n + 64 : 0) + (1ull << (memlevel + 6)) + 64;
 }
+// The trials of one batch on a pipe, by kind (0 stored, 1 fast, 2 slow levels), each with its slice of the
+// pipe's output and symbol scratch.  Every trial descriptor is made here (Round, strategy_pass, deflate_dev).
+struct TrialBatch {
+  std::vector<Trial> tr[3];
+  uint64_t out_tot = 0, sym_tot = 0;
+  // A trial of stream s (len inflated bytes) at (level, window, memLevel) under zlib strategy strat.
+  // Z_RLE and Z_HUFFMAN_ONLY ignore the level and read no tables (the stored kind's kernels); Z_FILTERED
+  // only changes deflate_slow, so on levels 1-3 it is the default strategy.  Returns (kind, index in tr[kind]).
+  std::pair<int, uint32_t> add(const Pipe* c, uint32_t s, uint64_t len, int cl, int w, int m, uint32_t strat,
+                               uint8_t mode, uint64_t best_ident) {
+    if (strat == 1 && cl < 4) strat = 0;
+    const int kind = cl == 0 || strat >= 2 ? 0 : cl <= 3 ? 1 : 2;
+    Trial t{};
+    t.stream = s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)m;
+    t.mode = mode; t.host = strat;
+    t.best_ident = best_ident;
+    t.out_off = out_tot; t.out_cap = bound(len, w, m) + 64;
+    out_tot += (t.out_cap + 255) & ~255ull;
+    t.sym_off = sym_tot; sym_tot += sym_words(c, kind, (uint32_t)m, len);
+    tr[kind].push_back(t);
+    return {kind, (uint32_t)tr[kind].size() - 1};
+  }
+  int reserve(Pipe* c) const {
+    if (int r = c->d_out.reserve(out_tot + 4096)) return r;
+    return c->d_syms.reserve(sym_tot * 4 + 4096);
+  }
+};
 
 // A launch lasts as long as its slowest wave, so the trials go in longest-expected-first order
 // (classic LPT): low memLevels mean many blocks (one tree build each), fast levels mean hole
@@ -1851,12 +1878,12 @@ static void trials_order(atz_ctx* x, const Pipe* c, std::vector<Trial>* in, Tria
     std::vector<uint64_t> key(n);
     const uint32_t mwm = c->mw_cap;
     const bool packed = n < (1u << 20);
-    bool strat = false;   // strategy trials (mode bits 6-7) among them
+    bool strat = false;   // strategy trials among them
     for (size_t q = 0; q < n; q++) {
       const Trial& t = in[k][q];
-      strat |= (t.mode >> 6) != 0;
+      strat |= (t.host & TH_STRAT) != 0;
       const uint64_t w = x->recs[t.stream].infl_len * (uint64_t)(k == 1 ? 3 : 1) * (uint64_t)(10 - t.memlevel) *
-                         (uint64_t)((t.mode & 8) ? 1 : 4);   // replays skip the match walks
+                         (uint64_t)((t.mode & TM_REPLAY) ? 1 : 4);   // replays skip the match walks
       const uint64_t mw = k != 0 && t.memlevel <= mwm;
       // with the stop flag, a stream's earlier trials of the round first: a stop they find ends the later
       // ones
@@ -1887,6 +1914,22 @@ static void trials_order(atz_ctx* x, const Pipe* c, std::vector<Trial>* in, Tria
 // the trial kernels over h[0, cnt) (one kind, multi-wave ones first), at slots [base, base + cnt)
 static int trials_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, const SweepOpts& so, int k, const Trial* h,
                          size_t cnt, size_t base) {
+  // the trial kernels by (kind, strategy, multi-wave); no row: no such trial.  (The rows' order is the
+  // order in which the templates are instantiated, and so the kernels' order in the code object.)
+  struct Kern { int kind; uint32_t strat; bool mw; void (*fn)(SweepArgs); const char* name; };
+  static const Kern kerns[] = {
+      {0, 0, false, k_trial_stored, "k_trial_stored"},
+      {0, 2, false, k_trial_huff, "k_trial_huff"},
+      {0, 3, false, k_trial_rle, "k_trial_rle"},
+      {1, 0, true, k_trial_fast_mw<BITMAP_BITS>, "k_trial_fast"},
+      {1, 0, false, k_trial_fast<BITMAP_BITS>, "k_trial_fast"},
+      {2, 0, true, k_trial_slow_mw, "k_trial_slow"},
+      {2, 0, false, k_trial_slow, "k_trial_slow"},
+      {2, 1, true, k_trial_slow_filt_mw, "k_trial_slow_filt"},
+      {2, 1, false, k_trial_slow_filt, "k_trial_slow_filt"},
+  };
+  for (size_t i = 0; i < cnt; i++)   // a waiting trial or a duplicate never reaches a launch
+    if (h[i].host & (TH_WAITS | TH_DUP)) return ATZ_E_INTERNAL;
   // the trial descriptors first, then the launches
   for (size_t i = 0; i < cnt;) {
     const bool mw = mw_trial(c, k, h[i].memlevel);
@@ -1898,8 +1941,10 @@ static int trials_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, const SweepO
   auto launch1 = [&](const Trial* hh, size_t n1, size_t b1, uint32_t variant) -> int {
     (void)hh;
     const bool mw = variant & 1u;
-    const uint32_t strat = variant >> 1;
-    if (strat && !((k == 2 && strat == 1) || (k == 0 && strat >= 2))) return ATZ_E_INTERNAL;
+    const Kern* kn = nullptr;
+    for (const Kern& e : kerns)
+      if (e.kind == k && e.strat == variant >> 1 && e.mw == mw) kn = &e;
+    if (!kn) return ATZ_E_INTERNAL;
     SweepArgs A;
     A.file = d_cmp; A.infl = INFL_BASE; A.chains = CHAIN_BASE;
     A.R = c->d_R.as<uint2>();
@@ -1909,18 +1954,9 @@ static int trials_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, const SweepO
     A.stopj = c->stopj_cur;
     dim3 g((uint32_t)n1), b(mw ? MW_THREADS : 64);
     kbeg(c, 0);
-    if (k == 0 && strat == 3) hipLaunchKernelGGL(k_trial_rle, g, b, 0, c->st, A);
-    else if (k == 0 && strat == 2) hipLaunchKernelGGL(k_trial_huff, g, b, 0, c->st, A);
-    else if (k == 2 && strat == 1 && mw) hipLaunchKernelGGL(k_trial_slow_filt_mw, g, b, 0, c->st, A);
-    else if (k == 2 && strat == 1) hipLaunchKernelGGL(k_trial_slow_filt, g, b, 0, c->st, A);
-    else if (k == 0) hipLaunchKernelGGL(k_trial_stored, g, b, 0, c->st, A);
-    else if (k == 1 && mw) hipLaunchKernelGGL(k_trial_fast_mw<BITMAP_BITS>, g, b, 0, c->st, A);
-    else if (k == 1) hipLaunchKernelGGL(k_trial_fast<BITMAP_BITS>, g, b, 0, c->st, A);
-    else if (mw) hipLaunchKernelGGL(k_trial_slow_mw, g, b, 0, c->st, A);
-    else hipLaunchKernelGGL(k_trial_slow, g, b, 0, c->st, A);
+    hipLaunchKernelGGL(kn->fn, g, b, 0, c->st, A);
     kend(c);
-    KCHECK(strat == 3 ? "k_trial_rle" : strat == 2 ? "k_trial_huff" : strat == 1 ? "k_trial_slow_filt"
-           : k == 0 ? "k_trial_stored" : k == 1 ? "k_trial_fast" : "k_trial_slow");
+    KCHECK(kn->name);
     return 0;
   };
   size_t i = 0;
@@ -1945,7 +1981,7 @@ static MatchJob first_match_job(atz_ctx* x, Pipe* c, int k, Trial& t) {
   const uint64_t n = x->recs[t.stream].infl_len;
   t.r_off = c->r_next;
   c->r_next += ((n + 63) & ~63ull) + 256;   // + the double-buffered window's over-read
-  t.x_lim = (t.mode & 3) || (mhint_on(x) && t.memlevel == x->recs[t.stream].mhint) ? n : match_prefix(n, t.memlevel, big_sweep(x));
+  t.x_lim = (t.mode & TM_FULL) || (mhint_on(x) && t.memlevel == x->recs[t.stream].mhint) ? n : match_prefix(n, t.memlevel, big_sweep(x));
   MatchJob m{};
   m.infl_off = x->infl_off[t.stream]; m.n = n; m.chain_off = t.chain_off; m.r_off = t.r_off;
   m.p0 = 0; m.p1 = t.x_lim; m.level = t.clevel; m.window = t.window; m.fast = k == 1; m.memlevel = t.memlevel;
@@ -1969,7 +2005,7 @@ static int trials_first_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, TrialS
   for (int k = 1; k < 3; k++)
     for (Trial& t : tr[k]) {
       const uint64_t n = x->recs[t.stream].infl_len;
-      if ((t.mode & 24) == 8) { t.r_off = 0; t.x_lim = n; continue; }   // unchecked replays: no match table
+      if (tm_unchecked_replay(t.mode)) { t.r_off = 0; t.x_lim = n; continue; }   // unchecked replays: no match table
       if (t.x_lim) continue;   // its table's first pass is already launched (Round::plan)
       if (MatchJob m = first_match_job(x, c, k, t); m.p1 > m.p0) mj.push_back(m);
     }
@@ -2099,14 +2135,14 @@ static bool dedup_on() {
 // lit_bufsize (at most lit_bufsize - 2 symbols: with lit_bufsize - 1 the tally flushes a block and the
 // end adds an empty final one) compresses to the saver's bytes: same symbols, same single block,
 // same header (level, window).  Its result can then only equal the saver's, which the stream's rule
-// already applied without stopping, so it is not launched (mode bit 7; TR_CANT_BEAT on the host).
+// already applied without stopping, so it is not launched (TH_DUP; TR_CANT_BEAT on the host).
 static void replay_from(Trial& t, const RpEntry& e, bool bf) {
   if (bf) {
-    t.mode |= 8;
+    t.mode |= TM_REPLAY;
     const uint32_t lm = std::min<uint32_t>(e.memlevel, t.memlevel);
-    if (dedup_on() && (uint64_t)e.nsym + 2 <= (1ull << (lm + 6))) t.mode |= 128;
+    if (dedup_on() && (uint64_t)e.nsym + 2 <= (1ull << (lm + 6))) t.host |= TH_DUP;
   } else if (e.tab) {
-    t.mode |= 8 | 16;
+    t.mode |= TM_REPLAY | TM_CHECKED;
     t.rp_tab = e.tab;
   } else {
     return;
@@ -2136,17 +2172,17 @@ static bool replay_free(atz_ctx* x, int kind, const Trial& t) {
 // nice_length (its walks would stop no earlier) and no lazy read improved a match of length >= L''s
 // max_lazy (the reads L' skips are ones that did not change the parse).  Same symbols, same
 // blocks, same header: the output, and so the result, is the earlier trial's, which the stream's
-// rule already applied without stopping.  Such a trial is not launched (mode bit 7).
+// rule already applied without stopping.  Such a trial is not launched (TH_DUP).
 static bool budget_free(atz_ctx* x, int kind, const Trial& t);
 static void level_dups(atz_ctx* x, std::vector<StreamState>& ss, std::vector<Trial>& slow) {
   for (Trial& t : slow) {
-    if (t.clevel < 7 || t.clevel > 9 || (t.mode & 1)) continue;
+    if (t.clevel < 7 || t.clevel > 9 || (t.mode & TM_FULL)) continue;
     const StreamState& st = ss[t.stream];
     for (const auto& r : st.xl) {
       // only a twin at a higher level: its lazy/nice bounds (main.cpp:739-745 lists levels descending)
       // are at least this level's, so it made every read this level would; r[2] < L proves nothing
       if (r[0] != t.window || r[1] != t.memlevel || r[2] <= t.clevel) continue;
-      if (r[3] < lazy_host(t.clevel) && r[4] < nice_host(t.clevel) && budget_free(x, 2, t)) t.mode |= 128;
+      if (r[3] < lazy_host(t.clevel) && r[4] < nice_host(t.clevel) && budget_free(x, 2, t)) t.host |= TH_DUP;
       break;
     }
   }
@@ -2161,7 +2197,7 @@ static void level_record(atz_ctx* x, std::vector<StreamState>& ss, const std::ve
     const Trial& t = slow[q];
     const TrialRes& r = res[q];
     if (!mine(t.stream)) continue;
-    if (t.clevel < 7 || t.clevel > 9 || (t.mode & 128) || r.state == TR_NEED_R || r.state == TR_OVERFLOW ||
+    if (t.clevel < 7 || t.clevel > 9 || (t.host & TH_DUP) || r.state == TR_NEED_R || r.state == TR_OVERFLOW ||
         r.state == TR_SKIPPED)
       continue;
     if (!budget_free(x, 2, t)) continue;
@@ -2192,7 +2228,7 @@ static void plan_replay(atz_ctx* x, Pipe* c, std::vector<StreamState>& ss, int k
   const bool checked = replay_mode() != 3 && kind == 2;   // ATZ_REPLAY=3: budget-free replays only
   for (size_t q = 0; q < trs.size(); q++) {
     Trial& t = trs[q];
-    if (t.clevel < 1 || t.clevel > 9 || (t.mode & (1 | 128))) continue;
+    if (t.clevel < 1 || t.clevel > 9 || (t.mode & TM_FULL) || (t.host & TH_DUP)) continue;
     const uint64_t n = x->recs[t.stream].infl_len;
     const uint64_t wsz = 1ull << t.window;
     if (n > wsz + (wsz - 262)) continue;                                  // the window may slide
@@ -2206,7 +2242,7 @@ static void plan_replay(atz_ctx* x, Pipe* c, std::vector<StreamState>& ss, int k
       if (replay_mode() == 2) continue;
       replay_from(t, x->rp_pool[st.rp][L - 1], bf);
     } else if (busy && same_w && replay_mode() != 2 && (bf || x->rp_pool[st.rp][L - 1].tab)) {
-      t.mode |= 64;   // its saver runs in this round: wait for it (second launch of the round)
+      t.host |= TH_WAITS;   // its saver runs in this round: wait for it (second launch of the round)
     } else if (!saved && !busy && bf) {
       if (st.rp < 0) {   // the pool holds one entry per stream at most: never past its reserve
         std::lock_guard<std::mutex> lk(x->rp_mu);
@@ -2226,9 +2262,9 @@ static void plan_replay(atz_ctx* x, Pipe* c, std::vector<StreamState>& ss, int k
       e.memlevel = t.memlevel;
       st.rp_busy |= (uint16_t)(1u << L);
       st.rp_win[L] = t.window;
-      t.mode |= 4;
+      t.mode |= TM_SAVE;
       t.rp_syms = e.addr;
-      if (e.tab) { t.mode |= 32; t.rp_tab = e.tab; }
+      if (e.tab) { t.mode |= TM_SAVE_TAB; t.rp_tab = e.tab; }
       savers.push_back({(uint32_t)kind, (uint32_t)q, (uint32_t)st.rp, (uint32_t)(t.clevel - 1)});   // indices: rp_pool may grow
     }
   }
@@ -2313,27 +2349,95 @@ static void account_trial(atz_ctx* x, Pipe* c, int k, const Trial& t, const Tria
   gk[5] += r.cyc_fallback; gk[6] += r.parsed; gk[7] += r.symbols; gk[8] += r.cyc_scan; gk[9] += r.cyc_send;
   for (int i = 0; i < 4; i++) gk[10 + i] += r.cyc_sec[i];
   // trial input read + compare read (bytes emitted and compared against the original)
-  if (!(t.mode & 128))   // duplicates are not launched; a trial never rerun stopped at its prefix
+  if (!(t.host & TH_DUP))   // duplicates are not launched; a trial never rerun stopped at its prefix
     c->stats.k_trial_alg_bytes += r.state == TR_NEED_R || r.state == TR_SKIPPED ? r.parsed
                                   : x->recs[t.stream].infl_len + (r.out_len < C ? r.out_len : C);
-  if (timing_level() >= 3 && !(t.mode & 128)) {
+  if (timing_level() >= 3 && !(t.host & TH_DUP)) {
     c->diag_rt.push_back({r.rt0, r.rt1});
     if (c->diag_path.size() <= t.stream) { c->diag_path.resize(x->recs.size(), 0); c->diag_ntr.resize(x->recs.size(), 0); }
     c->diag_path[t.stream] += (uint32_t)(r.rt1 - r.rt0);
     c->diag_ntr[t.stream]++;
   }
 }
+// A batch outside the sweep's rounds (strategy_pass, deflate_dev) gets bucket tables of its own: every
+// earlier table is dropped (the last batch's kernels are done: run_trials synchronised) and those of
+// `need` are built on pipe p, complete on return.
+static int private_chains(atz_ctx* c, Pipe* p, const std::vector<std::pair<uint32_t, int>>& need) {
+  for (auto& a : c->chain_off) a.fill(~0ull);
+  c->chain_arena.reset(cap_bytes(CHAIN_CACHE_CAP));
+  p->tmp_chains.clear();
+  p->chains_next = 0;
+  if (int r = ensure_chains(c, p, need)) return r;
+  HIPCHK(hipStreamSynchronize(p->st));
+  return 0;
+}
+
+// The reference's rule for one trial result of a stream of C compressed bytes (testDeflateParams and its
+// callers, main.cpp:685-700): `best`, the stream's best ident so far, rises on an improvement; the stream
+// stops on a full match or one within mismatch_tol; an improvement within recomp_tresh wants its
+// mismatch list (C - ident entries; diffs are only ever written for recompressible streams).
+struct RuleTally { uint64_t ntr = 0, nsc = 0, nhz = 0; };   // trials, shortcut exits, overlay hazards
+struct RuleStep { bool improved = false, stop = false, diff = false; };
+static int rule_step(const atz_opts_t& o, uint64_t C, const TrialRes& r, uint64_t& best, RuleTally& n, RuleStep& out) {
+  n.ntr++;
+  if (r.state == TR_SHORTCUT) n.nsc++;
+  if (r.flags & 1) n.nhz++;
+  if (r.state == TR_OVERFLOW) return ATZ_E_REF_ABORT;   // deflate() without Z_STREAM_END, main.cpp:663-665
+  out = RuleStep{};
+  if (r.state == TR_FULL && r.ident > best) {
+    best = r.ident;
+    out.improved = true;
+    out.stop = r.ident == C || r.ident + o.mismatch_tol >= C;
+    out.diff = r.ident != C && C - r.ident <= o.recomp_tresh;
+  }
+  return 0;
+}
+
+// Mismatch lists (main.cpp:699-714) of the jobs dj, from the trial outputs in the pipe's d_out: job q's
+// positions and values into pos[q] / val[q] (dj[q].cap entries each; dst is assigned here).
+static int run_diffs(Pipe* c, const uint8_t* d_file, std::vector<DiffJob>& dj, std::vector<std::vector<uint32_t>>& pos,
+                     std::vector<std::vector<uint8_t>>& val) {
+  pos.assign(dj.size(), {});
+  val.assign(dj.size(), {});
+  if (dj.empty()) return 0;
+  uint64_t dpos = 0;
+  for (DiffJob& d : dj) { d.dst = dpos; dpos += d.cap; }
+  if (int r = upload(c, c->d_diffjobs, dj.data(), dj.size() * sizeof(DiffJob))) return r;
+  if (int r = c->d_diffpos.reserve(dpos * 4 + 64)) return r;
+  if (int r = c->d_diffval.reserve(dpos + 64)) return r;
+  if (int r = c->d_diffcnt.reserve(dj.size() * 8 + 64)) return r;
+  kbeg(c, 3);
+  hipLaunchKernelGGL(k_diffs, dim3((uint32_t)dj.size()), dim3(64), 0, c->st, c->d_out.as<uint8_t>(), d_file,
+                     c->d_diffjobs.as<DiffJob>(), c->d_diffpos.as<uint32_t>(), c->d_diffval.as<uint8_t>(),
+                     c->d_diffcnt.as<uint64_t>(), (uint32_t)dj.size());
+  kend(c);
+  KCHECK("k_diffs");
+  std::vector<uint32_t> hp(dpos);
+  std::vector<uint8_t> hv(dpos);
+  std::vector<uint64_t> cnt(dj.size());
+  HIPCHK(pipe_copy(c, hp.data(), c->d_diffpos.p, dpos * 4, hipMemcpyDeviceToHost));
+  HIPCHK(pipe_copy(c, hv.data(), c->d_diffval.p, dpos, hipMemcpyDeviceToHost));
+  HIPCHK(pipe_copy(c, cnt.data(), c->d_diffcnt.p, dj.size() * 8, hipMemcpyDeviceToHost));
+  HIPCHK(pipe_sync(c));
+  kcollect(c);
+  for (size_t q = 0; q < dj.size(); q++) {
+    if (cnt[q] != dj[q].cap) return ATZ_E_INTERNAL;
+    pos[q].assign(hp.begin() + dj[q].dst, hp.begin() + dj[q].dst + dj[q].cap);
+    val[q].assign(hv.begin() + dj[q].dst, hv.begin() + dj[q].dst + dj[q].cap);
+  }
+  return 0;
+}
+
 // One round of pipe c over its batch `active`: the next K list entries of every stream (speculatively:
 // a stream that stops at its j-th trial discards the results of the later ones), K sized so the rounds
 // fill the GPU.  Results are applied per stream strictly in list order, so the outcome is the
 // reference's sequential one; the speculation only changes how much work runs per launch.
-struct Round {
+struct Round : TrialBatch {
   atz_ctx* x; Pipe* c; const uint8_t* d_file; std::vector<StreamState>& ss; const SweepOpts& so;
   std::vector<uint32_t>& active;
   std::vector<uint32_t>& waiting;   // streams the round's scratch budget left out (next round, first)
   uint32_t K = 1;
-  std::vector<Trial> tr[3];         // k = 0 stored, 1 fast, 2 slow levels
-  std::vector<TrialRes> trres[3];
+  std::vector<TrialRes> trres[3];   // of TrialBatch::tr (k = 0 stored, 1 fast, 2 slow levels)
   // per stream, its trials of this round in list order: stream a's are mine[mbeg[a] .. mbeg[a + 1]),
   // each (kind, index in tr[kind])
   std::vector<std::pair<int, uint32_t>> mine;
@@ -2341,7 +2445,6 @@ struct Round {
   std::vector<std::pair<uint32_t, int>> need;   // (stream, memLevel) pairs whose bucket tables trials read
   std::vector<uint32_t> need_b;                 // per need entry: the trial's walk budget (budget-free test)
   std::vector<std::array<uint32_t, 4>> savers;  // (kind, index in tr[kind], rp_pool entry, level - 1)
-  uint64_t out_tot = 0, sym_tot = 0;
   uint64_t r_bound = 0;             // d_R entries if every table-reading trial got a table (uint2 units)
   size_t nbuild = 0;
   // streams of the batch by index a into active: held[a] = its rule walk waits for a rerun
@@ -2352,7 +2455,8 @@ struct Round {
   struct PendDiff { bool live = false; DiffJob d{}; };
   std::vector<PendDiff> pend;      // a stream's live diff job: its latest improvement within recomp_tresh
   std::vector<uint32_t> jpos;      // where each stream's rule walk resumes
-  uint64_t ntr = 0, nsc = 0, nhz = 0, nspec = 0;
+  RuleTally tally;
+  uint64_t nspec = 0;
 
   Round(atz_ctx* x_, Pipe* c_, const uint8_t* f, std::vector<StreamState>& ss_, const SweepOpts& so_,
         std::vector<uint32_t>& a_, std::vector<uint32_t>& w_)
@@ -2382,23 +2486,18 @@ struct Round {
       for (uint32_t j = 0; j < K && st.idx + j < st.list->size(); j++) {
         const uint32_t p = (*st.list)[st.idx + j];
         const int cl = (int)(p >> 16), w = (int)((p >> 8) & 0xff), m = (int)(p & 0xff);
-        Trial t{};
-        t.stream = s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)m; t.mode = 0;
-        t.best_ident = st.ident;
+        const uint64_t len = x->recs[s].infl_len;
+        const auto at = add(c, s, len, cl, w, m, 0, 0, st.ident);
+        const int kind = at.first;
+        Trial& t = tr[kind][at.second];
         t.spec_j = j;
-        t.out_off = out_tot; t.out_cap = bound(x->recs[s].infl_len, w, m) + 64;
-        out_tot += (t.out_cap + 255) & ~255ull;
-        const int kind = cl == 0 ? 0 : cl <= 3 ? 1 : 2;
-        const uint64_t sw = sym_words(c, kind, (uint32_t)m, x->recs[s].infl_len);
-        t.sym_off = sym_tot; sym_tot += sw;
-        round_bytes += 8 * (x->recs[s].infl_len + 320) + t.out_cap + 4 * sw;
+        round_bytes += 8 * (len + 320) + t.out_cap + 4 * sym_words(c, kind, (uint32_t)m, len);
         if (kind) {
-          r_bound += ((x->recs[s].infl_len + 63) & ~63ull) + 256;
+          r_bound += ((len + 63) & ~63ull) + 256;
           need.push_back({s, m});
           need_b.push_back((uint32_t)(c_cfg_host((uint32_t)cl) >> (kind == 1 ? 0 : 2)));
         }
-        mine.push_back({kind, (uint32_t)tr[kind].size()});
-        tr[kind].push_back(t);
+        mine.push_back(at);
       }
     }
     mbeg.resize(active.size() + 1);
@@ -2487,11 +2586,11 @@ struct Round {
       need.clear();
       for (int k = 1; k < 3; k++)
         for (const Trial& t : tr[k])
-          if ((t.mode & 24) != 8 && !(t.mode & 128)) need.push_back({t.stream, (int)t.memlevel});
+          if (!tm_unchecked_replay(t.mode) && !(t.host & TH_DUP)) need.push_back({t.stream, (int)t.memlevel});
     }
     for (int k = 0; k < 3; k++)
       for (Trial& t : tr[k])
-        if (!(t.mode & 4)) t.best_ident = std::max(t.best_ident, elig_floor(x, x->recs[t.stream].comp_len));
+        if (!(t.mode & TM_SAVE)) t.best_ident = std::max(t.best_ident, elig_floor(x, x->recs[t.stream].comp_len));
     for (auto& q : need) nbuild += x->chain_off[q.first][q.second] == ~0ull;
     if (int r = ensure_chains(x, c, need)) return r;   // (stream-ordered before the match walks: no sync)
     for (int k = 1; k < 3; k++)
@@ -2501,17 +2600,16 @@ struct Round {
       }
     for (int k = 1; k < 3; k++)
       for (const Trial& t : tr[k])   // saved sequences stay inside the arena (a bad slot would fault the GPU)
-        if ((t.mode & 12) && !replay_slot_ok(t)) return ATZ_E_INTERNAL;
-    if (int r = c->d_out.reserve(out_tot + 4096)) return r;
-    if (int r = c->d_syms.reserve(sym_tot * 4 + 4096)) return r;
+        if ((t.mode & TM_RP_SYMS) && !replay_slot_ok(t)) return ATZ_E_INTERNAL;
+    if (int r = reserve(c)) return r;
     c->lap(4);
     return 0;
   }
   bool replay_slot_ok(const Trial& t) const {
     const uint64_t n = x->recs[t.stream].infl_len;
-    const bool syms_ok = !(t.mode & 12) || x->rp_arena.holds(t.rp_syms, 4 * (n + 64));
-    const bool tab_ok = !(t.mode & 48) || x->rp_arena.holds(t.rp_tab, 8 * n);
-    if (syms_ok && tab_ok && !((t.mode & 8) && t.rp_nsym > n)) return true;
+    const bool syms_ok = !(t.mode & TM_RP_SYMS) || x->rp_arena.holds(t.rp_syms, 4 * (n + 64));
+    const bool tab_ok = !(t.mode & TM_RP_TAB) || x->rp_arena.holds(t.rp_tab, 8 * n);
+    if (syms_ok && tab_ok && !((t.mode & TM_REPLAY) && t.rp_nsym > n)) return true;
     std::fprintf(stderr, "atz: symbol replay slot out of its arena (stream %u)\n", t.stream);
     return false;
   }
@@ -2548,13 +2646,13 @@ struct Round {
     TrialRes dup{};
     dup.state = TR_CANT_BEAT;
     for (int k = 1; k < 3; k++)
-      for (const Trial& t : tr[k]) waiting_trials |= (t.mode & 64) != 0;
+      for (const Trial& t : tr[k]) waiting_trials |= (t.host & TH_WAITS) != 0;
     {
       std::vector<Trial> ta[3];
       for (int k = 0; k < 3; k++) {
         trres[k].assign(tr[k].size(), dup);
         for (uint32_t q = 0; q < tr[k].size(); q++) {
-          if (tr[k][q].mode & (64 | 128)) continue;
+          if (tr[k][q].host & (TH_WAITS | TH_DUP)) continue;
           ta[k].push_back(tr[k][q]);
           ia[k].push_back(q);
         }
@@ -2579,12 +2677,12 @@ struct Round {
     for (int k = 1; k < 3; k++)
       for (uint32_t q = 0; q < tr[k].size(); q++) {
         Trial& t = tr[k][q];
-        if (!(t.mode & 64)) continue;
-        t.mode &= ~64u;
+        if (!(t.host & TH_WAITS)) continue;
+        t.host &= ~TH_WAITS;
         const RpEntry& e = x->rp_pool[ss[t.stream].rp][t.clevel - 1];
         if (e.state == 2 && e.window == t.window) replay_from(t, e, replay_free(x, k, t));
-        if (t.mode & 128) continue;
-        if ((t.mode & 8) && !replay_slot_ok(t)) return ATZ_E_INTERNAL;
+        if (t.host & TH_DUP) continue;
+        if ((t.mode & TM_REPLAY) && !replay_slot_ok(t)) return ATZ_E_INTERNAL;
         t3[k].push_back(t);
         ib[k].push_back(q);
       }
@@ -2615,30 +2713,17 @@ struct Round {
       }
       if (r.state == TR_SKIPPED) return ATZ_E_INTERNAL;   // only trials past the stream's stop end so
       st.trials++;
-      ntr++;
-      if (r.state == TR_SHORTCUT) nsc++;
-      if (r.flags & 1) nhz++;
-      if (r.state == TR_OVERFLOW) return ATZ_E_REF_ABORT;   // deflate() without Z_STREAM_END, main.cpp:663-665
-      bool fullmatch = false;
-      if (r.state == TR_FULL && r.ident > st.ident) {
-        st.ident = r.ident;
+      RuleStep step;
+      if (int e = rule_step(x->o, C, r, st.ident, tally, step)) return e;
+      if (step.improved) {
         st.c = t.clevel; st.w = t.window; st.m = t.memlevel;
         st.first_diff = -1;
         st.rawdiff.clear(); st.diffval.clear();
-        pend[a].live = false;   // an earlier improvement's diffs are superseded
-        if (r.ident == C) fullmatch = true;
-        else {
-          if (r.ident + x->o.mismatch_tol >= C) fullmatch = true;
-          if (C - r.ident <= x->o.recomp_tresh) {     // diffs are only ever written for recomp streams
-            DiffJob& d = pend[a].d;
-            d.out_off = t.out_off; d.out_len = r.out_len; d.orig_off = x->recs[s].offset;
-            d.comp_len = C; d.dst = 0; d.cap = C - r.ident;
-            pend[a].live = true;
-          }
-        }
+        pend[a].live = step.diff;   // an earlier improvement's diffs are superseded
+        if (step.diff) pend[a].d = DiffJob{t.out_off, r.out_len, x->recs[s].offset, C, 0, C - r.ident};
       }
       st.idx++;
-      if (fullmatch) st.idx = (uint32_t)st.list->size();   // testParamRange/tryParams return
+      if (step.stop) st.idx = (uint32_t)st.list->size();   // testParamRange/tryParams return
       if (st.idx >= st.list->size()) {
         if (st.phase == 0 && (C - st.ident) >= x->o.mismatch_tol && x->o.brute_window) {
           st.list = &trial_list(x->recs[s].type, true);
@@ -2705,40 +2790,18 @@ struct Round {
   int flush_diffs() {
     std::vector<DiffJob> dj;
     std::vector<size_t> dja;
-    uint64_t dpos = 0;
     for (size_t a = 0; a < active.size(); a++) {
       if (!pend[a].live) continue;
       pend[a].live = false;
-      DiffJob d = pend[a].d;
-      d.dst = dpos;
-      dpos += d.cap;
-      dj.push_back(d);
+      dj.push_back(pend[a].d);
       dja.push_back(a);
     }
-    if (dj.empty()) return 0;
-    if (int r = upload(c, c->d_diffjobs, dj.data(), dj.size() * sizeof(DiffJob))) return r;
-    if (int r = c->d_diffpos.reserve(dpos * 4 + 64)) return r;
-    if (int r = c->d_diffval.reserve(dpos + 64)) return r;
-    if (int r = c->d_diffcnt.reserve(dj.size() * 8 + 64)) return r;
-    kbeg(c, 3);
-    hipLaunchKernelGGL(k_diffs, dim3((uint32_t)dj.size()), dim3(64), 0, c->st, c->d_out.as<uint8_t>(), d_file,
-                       c->d_diffjobs.as<DiffJob>(), c->d_diffpos.as<uint32_t>(), c->d_diffval.as<uint8_t>(),
-                       c->d_diffcnt.as<uint64_t>(), (uint32_t)dj.size());
-    kend(c);
-    KCHECK("k_diffs");
-    std::vector<uint32_t> pos(dpos);
-    std::vector<uint8_t> val(dpos);
-    std::vector<uint64_t> cnt(dj.size());
-    HIPCHK(pipe_copy(c, pos.data(), c->d_diffpos.p, dpos * 4, hipMemcpyDeviceToHost));
-    HIPCHK(pipe_copy(c, val.data(), c->d_diffval.p, dpos, hipMemcpyDeviceToHost));
-    HIPCHK(pipe_copy(c, cnt.data(), c->d_diffcnt.p, dj.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(pipe_sync(c));
-    kcollect(c);
+    std::vector<std::vector<uint32_t>> pos;
+    std::vector<std::vector<uint8_t>> val;
+    if (int r = run_diffs(c, d_file, dj, pos, val)) return r;
     for (size_t q = 0; q < dj.size(); q++) {
-      if (cnt[q] != dj[q].cap) return ATZ_E_INTERNAL;
       StreamState& st = ss[active[dja[q]]];
-      st.rawdiff.assign(pos.begin() + dj[q].dst, pos.begin() + dj[q].dst + dj[q].cap);
-      st.diffval.assign(val.begin() + dj[q].dst, val.begin() + dj[q].dst + dj[q].cap);
+      st.rawdiff.swap(pos[q]); st.diffval.swap(val[q]);
       st.first_diff = st.rawdiff.empty() ? -1 : (int64_t)st.rawdiff[0];
     }
     return 0;
@@ -2750,9 +2813,9 @@ struct Round {
     for (int k = 1; k < 3; k++)
       for (size_t q = 0; q < tr[k].size(); q++) {
         c->stats.n_trials_replayed += (trres[k][q].saved_flags >> 2) & 1u;
-        c->stats.n_replay_checked += (tr[k][q].mode >> 4) & 1u;
-        c->stats.n_trials_duplicate += (tr[k][q].mode >> 7) & 1u;
-        if (timing_on() && (tr[k][q].mode & 24) != 8 && !(tr[k][q].mode & 128)) {
+        c->stats.n_replay_checked += (tr[k][q].mode & TM_CHECKED) != 0;
+        c->stats.n_trials_duplicate += (tr[k][q].host & TH_DUP) != 0;
+        if (timing_on() && !tm_unchecked_replay(tr[k][q].mode) && !(tr[k][q].host & TH_DUP)) {
           if (c->diag_need.size() <= tr[k][q].stream) c->diag_need.resize(tr[k][q].stream + 1, 0);
           c->diag_need[tr[k][q].stream] |= (uint16_t)(1u << tr[k][q].memlevel);
         }
@@ -2764,7 +2827,7 @@ struct Round {
       std::vector<uint32_t> st0, en;
       for (int k = 0; k < 3; k++)
         for (size_t q = 0; q < tr[k].size(); q++)
-          if (!(tr[k][q].mode & 128) && trres[k][q].rt1) { st0.push_back(trres[k][q].rt0); en.push_back(trres[k][q].rt1); }
+          if (!(tr[k][q].host & TH_DUP) && trres[k][q].rt1) { st0.push_back(trres[k][q].rt0); en.push_back(trres[k][q].rt1); }
       if (!en.empty()) {
         const uint32_t b = *std::min_element(st0.begin(), st0.end());
         std::sort(en.begin(), en.end());
@@ -2836,7 +2899,7 @@ static int sweep_pipe(atz_ctx* x, Pipe* c, const uint8_t* d_file, std::vector<St
     R.account(rounds);
     c->lap(12);
     c->t_apply += ms_since(tc);
-    c->stats.n_trials += R.ntr; c->stats.n_trials_shortcut += R.nsc; c->stats.n_hazard += R.nhz;
+    c->stats.n_trials += R.tally.ntr; c->stats.n_trials_shortcut += R.tally.nsc; c->stats.n_hazard += R.tally.nhz;
     c->stats.n_trials_speculative += R.nspec;
   }
   c->stats.n_rounds = rounds;
@@ -3205,8 +3268,7 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
   const atz_stats_t before = p->stats;
   const SweepOpts so{c->o.recomp_tresh, c->o.sizediff_tresh, c->o.shortcut_len, c->o.mismatch_tol};
   const uint64_t budget = cap_bytes(ROUND_BUDGET_BYTES);
-  for (auto& a : c->chain_off) a.fill(~0ull);
-  uint64_t ntr = 0, nsc = 0, nhz = 0;
+  RuleTally tally;
   for (size_t j = 0; j < longest; j++) {
     std::vector<uint32_t> act;
     for (uint32_t s : todo)
@@ -3221,98 +3283,51 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
         bytes += 9 * len + 4 * sym_words(p, 2, q & 0xff, len) + bound(len, (int)((q >> 8) & 0xff), (int)(q & 0xff)) + 4096;
         a1++;
       }
-      for (size_t a = a0; a < a1; a++) c->chain_off[act[a]].fill(~0ull);
-      c->chain_arena.reset(cap_bytes(CHAIN_CACHE_CAP));   // the last batch's kernels are done (run_trials synchronised)
-      p->tmp_chains.clear();
-      p->chains_next = 0;
       std::vector<std::pair<uint32_t, int>> need;
       for (size_t a = a0; a < a1; a++) {
         const uint32_t q = ex[act[a]].list[j];
         if ((q >> 24) == 1) need.push_back({act[a], (int)(q & 0xff)});
       }
-      if (int r = ensure_chains(c, p, need)) return r;
-      HIPCHK(hipStreamSynchronize(p->st));
-      std::vector<Trial> tr[3];
-      std::vector<uint32_t> who[3];
-      uint64_t out_tot = 0, sym_tot = 0;
+      if (int r = private_chains(c, p, need)) return r;
+      TrialBatch B;   // never saves, replays or stands for a duplicate
       for (size_t a = a0; a < a1; a++) {
         const uint32_t s = act[a], q = ex[s].list[j];
-        const uint32_t strat = q >> 24;
-        const int cl = (int)((q >> 16) & 0xff), w = (int)((q >> 8) & 0xff), m = (int)(q & 0xff);
-        const uint64_t len = c->recs[s].infl_len;
-        Trial t{};
-        t.stream = s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)m;
-        t.mode = (uint8_t)(strat << 6);   // never saves, replays or stands for a duplicate
-        t.best_ident = std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len));
-        t.out_off = out_tot; t.out_cap = bound(len, w, m) + 64;
-        out_tot += (t.out_cap + 255) & ~255ull;
-        const int kind = strat == 1 ? 2 : 0;
-        t.sym_off = sym_tot; sym_tot += sym_words(p, kind, (uint32_t)m, len);
-        if (kind) t.chain_off = c->chain_off[s][m];
-        tr[kind].push_back(t);
-        who[kind].push_back(s);
+        const int m = (int)(q & 0xff);
+        const auto at = B.add(p, s, c->recs[s].infl_len, (int)((q >> 16) & 0xff), (int)((q >> 8) & 0xff), m, q >> 24, 0,
+                              std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len)));
+        if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m];
       }
-      if (int r = p->d_out.reserve(out_tot + 4096)) return r;
-      if (int r = p->d_syms.reserve(sym_tot * 4 + 4096)) return r;
+      if (int r = B.reserve(p)) return r;
       std::vector<TrialRes> rr[3];
-      if (int r = run_trials(c, p, d_file, tr, so, rr)) return r;
-      // the rule (main.cpp:685-700) on each stream's trial; mismatch lists (main.cpp:699-714) of the
-      // improvements within recomp_tresh from the outputs, which the next batch overwrites
+      if (int r = run_trials(c, p, d_file, B.tr, so, rr)) return r;
+      // the rule on each stream's trial; the mismatch lists of the improvements within recomp_tresh from
+      // the outputs, which the next batch overwrites
       std::vector<DiffJob> dj;
       std::vector<uint32_t> djs;
-      uint64_t dpos = 0;
-      for (int k = 0; k < 3; k += 2)
-        for (size_t q = 0; q < tr[k].size(); q++) {
-          const Trial& t = tr[k][q];
+      for (int k = 0; k < 3; k++)
+        for (size_t q = 0; q < B.tr[k].size(); q++) {
+          const Trial& t = B.tr[k][q];
           const TrialRes& r = rr[k][q];
-          const uint32_t s = who[k][q];
+          const uint32_t s = t.stream;
           const uint64_t C = c->recs[s].comp_len;
           Ext& e = ex[s];
           if (r.state == TR_NEED_R || r.state == TR_SKIPPED) return ATZ_E_INTERNAL;
-          if (r.state == TR_OVERFLOW) return ATZ_E_REF_ABORT;   // deflate() without Z_STREAM_END, main.cpp:663-665
           ss[s].trials++;
-          ntr++;
-          nsc += r.state == TR_SHORTCUT;
-          nhz += r.flags & 1;
-          if (r.state != TR_FULL || r.ident <= e.ident) continue;
-          e.ident = r.ident;
+          RuleStep step;
+          if (int err = rule_step(c->o, C, r, e.ident, tally, step)) return err;
+          if (!step.improved) continue;
           e.best = e.list[j];
           e.rawdiff.clear(); e.diffval.clear();
-          if (r.ident == C || r.ident + c->o.mismatch_tol >= C) e.done = true;
-          if (r.ident != C && C - r.ident <= c->o.recomp_tresh) {
-            DiffJob d{};
-            d.out_off = t.out_off; d.out_len = r.out_len; d.orig_off = c->recs[s].offset;
-            d.comp_len = C; d.dst = dpos; d.cap = C - r.ident;
-            dpos += d.cap;
-            dj.push_back(d);
+          e.done = step.stop;
+          if (step.diff) {
+            dj.push_back(DiffJob{t.out_off, r.out_len, c->recs[s].offset, C, 0, C - r.ident});
             djs.push_back(s);
           }
         }
-      if (!dj.empty()) {
-        if (int r = upload(p, p->d_diffjobs, dj.data(), dj.size() * sizeof(DiffJob))) return r;
-        if (int r = p->d_diffpos.reserve(dpos * 4 + 64)) return r;
-        if (int r = p->d_diffval.reserve(dpos + 64)) return r;
-        if (int r = p->d_diffcnt.reserve(dj.size() * 8 + 64)) return r;
-        kbeg(p, 3);
-        hipLaunchKernelGGL(k_diffs, dim3((uint32_t)dj.size()), dim3(64), 0, p->st, p->d_out.as<uint8_t>(), d_file,
-                           p->d_diffjobs.as<DiffJob>(), p->d_diffpos.as<uint32_t>(), p->d_diffval.as<uint8_t>(),
-                           p->d_diffcnt.as<uint64_t>(), (uint32_t)dj.size());
-        kend(p);
-        std::vector<uint32_t> pos(dpos);
-        std::vector<uint8_t> val(dpos);
-        std::vector<uint64_t> cnt(dj.size());
-        HIPCHK(pipe_copy(p, pos.data(), p->d_diffpos.p, dpos * 4, hipMemcpyDeviceToHost));
-        HIPCHK(pipe_copy(p, val.data(), p->d_diffval.p, dpos, hipMemcpyDeviceToHost));
-        HIPCHK(pipe_copy(p, cnt.data(), p->d_diffcnt.p, dj.size() * 8, hipMemcpyDeviceToHost));
-        HIPCHK(pipe_sync(p));
-        kcollect(p);
-        for (size_t q = 0; q < dj.size(); q++) {
-          if (cnt[q] != dj[q].cap) return ATZ_E_INTERNAL;
-          Ext& e = ex[djs[q]];
-          e.rawdiff.assign(pos.begin() + dj[q].dst, pos.begin() + dj[q].dst + dj[q].cap);
-          e.diffval.assign(val.begin() + dj[q].dst, val.begin() + dj[q].dst + dj[q].cap);
-        }
-      }
+      std::vector<std::vector<uint32_t>> pos;
+      std::vector<std::vector<uint8_t>> val;
+      if (int r = run_diffs(p, d_file, dj, pos, val)) return r;
+      for (size_t q = 0; q < dj.size(); q++) { ex[djs[q]].rawdiff.swap(pos[q]); ex[djs[q]].diffval.swap(val[q]); }
       a0 = a1;
     }
   }
@@ -3331,14 +3346,14 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
   }
   atz_stats_t& t = c->stats;
   const atz_stats_t& q = p->stats;
-  t.n_trials += ntr; t.n_trials_shortcut += nsc; t.n_hazard += nhz;
+  t.n_trials += tally.ntr; t.n_trials_shortcut += tally.nsc; t.n_hazard += tally.nhz;
   t.k_trial_ms += q.k_trial_ms - before.k_trial_ms; t.k_trial_launches += q.k_trial_launches - before.k_trial_launches;
   t.k_chains_ms += q.k_chains_ms - before.k_chains_ms; t.k_chains_launches += q.k_chains_launches - before.k_chains_launches;
   t.k_match_ms += q.k_match_ms - before.k_match_ms; t.k_match_launches += q.k_match_launches - before.k_match_launches;
   t.k_other_ms += q.k_other_ms - before.k_other_ms;
   t.sweep_ms += ms_since(t0);
   if (timing_on()) std::fprintf(stderr, "atz: strategy pass: %zu streams, %llu trials  %9.2f ms\n", todo.size(),
-                                (unsigned long long)ntr, ms_since(t0));
+                                (unsigned long long)tally.ntr, ms_since(t0));
   return 0;
 }
 
@@ -3636,46 +3651,29 @@ static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std:
       s1++;
     }
     c->chain_off.assign(n, {});
-    for (auto& a2 : c->chain_off) a2.fill(~0ull);
-    c->chain_arena.reset(cap_bytes(CHAIN_CACHE_CAP));   // the last batch's kernels are done (run_trials synchronised)
-    p->tmp_chains.clear();
-    p->chains_next = 0;
     std::vector<std::pair<uint32_t, int>> need;
     // (params carry a strategy in bits 24-25: Z_RLE and Z_HUFFMAN_ONLY read no bucket tables)
     for (size_t s = s0; s < s1; s++)
       if (((params[s] >> 16) & 0xff) > 0 && (params[s] >> 24) < 2) need.push_back({(uint32_t)s, (int)(params[s] & 0xff)});
-    if (int r = ensure_chains(c, p, need)) return r;
-    HIPCHK(hipStreamSynchronize(p->st));
-    std::vector<Trial> tr[3];
-    std::vector<uint32_t> idx[3];
-    uint64_t out_tot = 0, sym_tot = 0;
+    if (int r = private_chains(c, p, need)) return r;
+    TrialBatch B;
     for (size_t s = s0; s < s1; s++) {
-      const int cl = (int)((params[s] >> 16) & 0xff), w = (int)((params[s] >> 8) & 0xff), m = (int)(params[s] & 0xff);
-      // Z_FILTERED only changes deflate_slow (levels 4-9); Z_RLE / Z_HUFFMAN_ONLY replace the level's parse
-      const uint32_t sg = params[s] >> 24, strat = sg == 1 && cl < 4 ? 0u : sg;
-      Trial t{};
-      t.stream = (uint32_t)s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)m;
-      t.mode = (uint8_t)(1u | (strat << 6));
-      t.best_ident = 0; t.out_off = out_tot; t.out_cap = bound(len[s], w, m) + 64;
-      out_tot += (t.out_cap + 255) & ~255ull;
-      const int kind = cl == 0 || strat >= 2 ? 0 : cl <= 3 ? 1 : 2;
-      t.sym_off = sym_tot; sym_tot += sym_words(p, kind, (uint32_t)m, len[s]);
-      if (kind) t.chain_off = c->chain_off[s][m];
-      tr[kind].push_back(t);
-      idx[kind].push_back((uint32_t)s);
+      const int m = (int)(params[s] & 0xff);
+      const auto at = B.add(p, (uint32_t)s, len[s], (int)((params[s] >> 16) & 0xff), (int)((params[s] >> 8) & 0xff), m,
+                            params[s] >> 24, TM_FULL, 0);
+      if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m];
     }
-    if (int r = p->d_out.reserve(out_tot + 4096)) return r;
-    if (int r = p->d_syms.reserve(sym_tot * 4 + 4096)) return r;
+    if (int r = B.reserve(p)) return r;
     SweepOpts so{0, 0, 0, 0};
     std::vector<TrialRes> rr[3];
-    if (int r = run_trials(c, p, c->d_tmp.as<uint8_t>(), tr, so, rr)) return r;
+    if (int r = run_trials(c, p, c->d_tmp.as<uint8_t>(), B.tr, so, rr)) return r;
     std::vector<uint64_t> oa(s1 - s0), ol(s1 - s0);
     const uint64_t ob = (uint64_t)(uintptr_t)p->d_out.p;
     for (int k = 0; k < 3; k++)
-      for (size_t q = 0; q < tr[k].size(); q++) {
+      for (size_t q = 0; q < B.tr[k].size(); q++) {
         if (rr[k][q].state != TR_FULL) return ATZ_E_INTERNAL;
-        oa[idx[k][q] - s0] = ob + tr[k][q].out_off;
-        ol[idx[k][q] - s0] = rr[k][q].out_len;
+        oa[B.tr[k][q].stream - s0] = ob + B.tr[k][q].out_off;
+        ol[B.tr[k][q].stream - s0] = rr[k][q].out_len;
       }
     if (int r = on_batch(s0, s1, oa, ol)) return r;
     s0 = s1;

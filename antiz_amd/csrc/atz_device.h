@@ -46,9 +46,25 @@ struct InfRes {
 };
 
 // ---- deflate trial (k_trial) ---------------------------------------------------------------
+// Trial::mode: the flags the trial kernels read (TrialRun's constructor), and nothing else
+enum : uint8_t {
+  TM_FULL = 1,        // full output needed (no early exits)
+  TM_SAVE = 4,        // saves its whole symbol sequence at rp_syms
+  TM_REPLAY = 8,      // replays the rp_nsym symbols saved at rp_syms instead of parsing
+  TM_CHECKED = 16,    // with TM_REPLAY: only if its own match table equals the one saved at rp_tab (else it parses)
+  TM_SAVE_TAB = 32,   // with TM_SAVE: records the match-table entries its parse reads at rp_tab
+  TM_RP_SYMS = TM_SAVE | TM_REPLAY,        // rp_syms is read or written
+  TM_RP_TAB = TM_CHECKED | TM_SAVE_TAB,    // rp_tab is read or written
+};
+// Trial::host: the host's bookkeeping (no kernel reads it; the strategy reaches a kernel as a template argument)
+enum : uint32_t {
+  TH_STRAT = 3,   // mask: zlib's strategy number (0 default, 1 Z_FILTERED, 2 Z_HUFFMAN_ONLY, 3 Z_RLE)
+  TH_WAITS = 4,   // waits for a saver of this round (launched in the round's second set)
+  TH_DUP = 8,     // a duplicate of an earlier trial's result: not launched
+};
 struct Trial {
   uint32_t stream;   // index into the stream table
-  uint8_t clevel, window, memlevel, mode;  // mode bit0: full output needed (no early exits)
+  uint8_t clevel, window, memlevel, mode;  // mode: TM_* flags
   uint64_t best_ident;  // best ident of this stream before this round (for the can't-beat exit)
   uint64_t out_off;     // scratch output offset for this trial (bytes)
   uint64_t out_cap;     // scratch output capacity (bytes)
@@ -56,17 +72,20 @@ struct Trial {
   uint64_t chain_off;   // hash buckets of (stream, memlevel) (uint32 units, k_buckets); unused for level 0
   uint64_t r_off;       // match table of this trial (uint2 units, indexed by absolute position)
   uint64_t x_lim;       // match-table entries exist for positions < x_lim (else the trial stops: TR_NEED_R)
-  // symbol replay: mode bit2 = this trial saves its whole symbol sequence at rp_syms (bit5: and its
-  // match table at rp_tab); bit3 = this trial replays the rp_nsym symbols saved there (rp_flags bit1:
-  // the last one is deflate_slow's end-of-input pending literal) instead of parsing -- with bit4 only
-  // if its own match table equals the one saved at rp_tab (else it parses)
+  // symbol replay: a TM_SAVE trial saves its whole symbol sequence at rp_syms (TM_SAVE_TAB: and its
+  // match table at rp_tab); a TM_REPLAY trial replays the rp_nsym symbols saved there (rp_flags bit1:
+  // the last one is deflate_slow's end-of-input pending literal) instead of parsing -- with TM_CHECKED
+  // only if its own match table equals the one saved at rp_tab (else it parses)
   uint64_t rp_syms;     // absolute device address (u32 symbols)
   uint64_t rp_tab;      // absolute device address (uint2 match-table entries)
   uint32_t rp_nsym, rp_flags;
   // speculative rounds: the trial's place among its stream's trials of the round (0: the first); a trial
   // whose stream an earlier one of the round has already stopped ends at once (SweepArgs::stopj)
-  uint32_t spec_j, pad2_;
+  uint32_t spec_j, host;   // host: TH_* (host only)
 };
+static_assert(sizeof(Trial) == 96, "the trial kernels load this layout");
+// a replay that reads no match table (none is built for it)
+static inline bool tm_unchecked_replay(uint8_t mode) { return (mode & (TM_REPLAY | TM_CHECKED)) == TM_REPLAY; }
 
 // ---- match tables (k_match) ----------------------------------------------------------------
 // longest_match (Z/deflate.c:1148-1289) evaluated for every position p of a stream, one lane per
@@ -104,7 +123,7 @@ struct TrialRes {
   uint64_t cyc_heap, cyc_fallback;                  // tree heap steps (ATZ_STEP_CLOCKS) / fast-level exact walks
   uint64_t cyc_scan, cyc_send;                      // scan_tree / send_tree (ATZ_STEP_CLOCKS)
   uint64_t cyc_sec[4];                              // parse window phases: refill / steps / path / tally (ATZ_STEP_CLOCKS)
-  uint32_t saved_syms;  // mode bit2: symbols saved at rp_syms
+  uint32_t saved_syms;  // TM_SAVE: symbols saved at rp_syms
   uint32_t saved_flags; // bit0: the whole input was parsed (the sequence is complete), bit1: end-of-input
                         // literal, bit2: the trial replayed a saved sequence
   uint32_t reads_max;   // slow parses: (longest prev_length a lazy read improved) << 16 | longest length read

@@ -1976,8 +1976,8 @@ static constexpr uint32_t TR_DECIDED = 0xfffffffeu;   // parser-side: a flusher 
 // deflate_slow -- with its blocks flushed as they fill, then the trailer and the final gates.  The
 // parse state lives in the members (registers, once everything is inlined).
 // KIND: 0 deflate_stored, 1 deflate_fast, 2 deflate_slow, 3 deflate_rle, 4 deflate_huff (the last two take
-// no chains and no match table).  STRAT: 1 = deflate_slow under Z_FILTERED (Trial::mode bits 6-7 carry
-// zlib's strategy number: the host picks the instantiation by it).
+// no chains and no match table).  STRAT: 1 = deflate_slow under Z_FILTERED (Trial::host carries zlib's
+// strategy number, which no kernel reads: the host picks the instantiation by it).
 template <int KIND, typename SH, int STRAT = 0>
 struct TrialRun {
   static constexpr bool MW = HasMW<SH>::value;
@@ -2031,7 +2031,7 @@ struct TrialRun {
         stg((LDS uint32_t*)shm_.ring), b(s.b), t(blockIdx.x), tr(A_.trials[t]), sd(A_.streams[tr.stream]),
         in(A_.infl + sd.infl_off), npad((uint32_t)((sd.infl_len + 63) & ~63ull)),
         sidx(!TAB ? nullptr : A_.chains + tr.chain_off), bpos(!TAB ? nullptr : sidx + npad),
-        full_needed(tr.mode & 1), lt(lane_ ? (~0ull >> (64 - lane_)) : 0ull) {
+        full_needed(tr.mode & TM_FULL), lt(lane_ ? (~0ull >> (64 - lane_)) : 0ull) {
     z.level = tr.clevel; z.kind = KIND;
     z.wsize = 1u << tr.window; z.maxdist = z.wsize - LOOKMIN; z.lbs = 1u << (tr.memlevel + 6);
     z.good = c_cfg[z.level][0]; z.lazy = c_cfg[z.level][1]; z.nice = c_cfg[z.level][2]; z.chain = c_cfg[z.level][3];
@@ -2046,9 +2046,9 @@ struct TrialRun {
     }
     // fast and slow levels: a saving trial writes its whole symbol sequence at rp_syms (block k's
     // symbols at sbase, the count of symbols in the blocks before it); a replaying trial reads one
-    saving = TAB && (tr.mode & 4);
-    replay = TAB && (tr.mode & 8);
-    if (KIND == 2 && replay && (tr.mode & 16)) {
+    saving = TAB && (tr.mode & TM_SAVE);
+    replay = TAB && (tr.mode & TM_REPLAY);
+    if (KIND == 2 && replay && (tr.mode & TM_CHECKED)) {
       const uint32_t tlim = tr.x_lim < sd.infl_len ? (uint32_t)tr.x_lim : (uint32_t)sd.infl_len;   // entries present
       // replay only if this trial's table agrees with the saver's on every entry the saver's parse
       // read (bit 0 of a saved half: that half was read): then this trial's parse reads the same
@@ -2074,7 +2074,7 @@ struct TrialRun {
     }
     syms = saving || replay ? (GLOBAL uint32_t*)(uintptr_t)tr.rp_syms : (GLOBAL uint32_t*)(A.syms + tr.sym_off);
     // a saving slow trial records the match-table entries its parse reads (rp_tab, cleared first)
-    rec = KIND == 2 && saving && (tr.mode & 32);
+    rec = KIND == 2 && saving && (tr.mode & TM_SAVE_TAB);
     rtab = (GLOBAL uint64_t*)(uintptr_t)tr.rp_tab;
     if (rec && wave == 0) {
       for (uint32_t p = (uint32_t)lane; p < sd.infl_len; p += 64) rtab[p] = 0;
@@ -3152,7 +3152,7 @@ __global__ __launch_bounds__(MW_THREADS, TRIAL_SLOW_WAVES) void k_trial_slow_mw(
   __shared__ TrialSharedSlowMW shm;
   trial_body<2>(A, shm, (int)(threadIdx.x & 63));
 }
-// Strategy trials (Trial::mode bits 6-7; opt-in): deflate_slow under Z_FILTERED on the
+// Strategy trials (Trial::host & TH_STRAT; opt-in): deflate_slow under Z_FILTERED on the
 // default strategy's chains and match tables, and deflate_rle / deflate_huff, which need neither (the ring
 // only holds the tree scratch and the emission staging)
 __global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_slow_filt(SweepArgs A) {
