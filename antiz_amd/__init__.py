@@ -54,7 +54,8 @@ class Stats(C.Structure):
 EXPORTS = ["atz_open", "atz_close", "atz_strerror", "atz_free", "atz_default_opts", "atz_scan", "atz_sweep",
            "atz_precompress", "atz_precompress_device", "atz_reconstruct", "atz_deflate", "atz_deflate_batch",
            "atz_inflate_batch", "atz_deflate_bound", "atz_shard_scan", "atz_shard_sweep", "atz_shard_piece",
-           "atz_shard_assemble", "atz_reconstruct_device", "atz_deflate_batch_ex", "atz_set_strategies"]
+           "atz_shard_assemble", "atz_reconstruct_device", "atz_deflate_batch_ex", "atz_set_strategies",
+           "atz_set_containers", "atz_container_anchors"]
 
 # zlib's strategy numbers (Z_FIXED, 4, is not supported); a strategy mask has bit k set for strategy k
 STRATEGIES = {"filtered": 1, "huffman": 2, "rle": 3}
@@ -72,16 +73,37 @@ def strategy_mask(names):
     return mask
 
 
-def pack_clevel(strategy, level):
-    """The clevel byte of an ATZ2 descriptor (and of atz_sweep's results): strategy << 4 | level."""
+# containers whose raw deflate bodies a container mask makes the scan look for: bit number of each
+CONTAINERS = {"zip": 0, "gzip": 1}
+
+
+def container_mask(names):
+    """("zip", "gzip") or a comma-separated string -> atz_set_containers mask; ValueError on an unknown word."""
+    if isinstance(names, str):
+        names = [w for w in names.split(",") if w]
+    mask = 0
+    for w in names:
+        if w not in CONTAINERS:
+            raise ValueError("unknown container %r (known: %s)" % (w, ", ".join(sorted(CONTAINERS))))
+        mask |= 1 << CONTAINERS[w]
+    return mask
+
+
+def pack_clevel(strategy, level, raw=False):
+    """The clevel byte of an ATZ2 / ATZ3 descriptor (and of atz_sweep's results): raw << 6 | strategy << 4 | level."""
     if not (0 <= strategy <= 3 and 0 <= level <= 9) or (strategy >= 2 and level < 1):
         raise ValueError("strategy %d with level %d" % (strategy, level))
-    return (strategy << 4) | level
+    return (int(bool(raw)) << 6) | (strategy << 4) | level
 
 
 def unpack_clevel(b):
     """-> (strategy, level) of a clevel byte."""
     return b >> 4, b & 15
+
+
+def unpack_clevel3(b):
+    """-> (raw, strategy, level) of an ATZ3 clevel byte."""
+    return bool(b & 0x40), (b >> 4) & 3, b & 15
 
 _lib = None
 
@@ -123,6 +145,9 @@ def lib():
                                         C.POINTER(u64)]
         L.atz_deflate_batch_ex.argtypes = L.atz_deflate_batch.argtypes
         L.atz_set_strategies.argtypes = [C.c_void_p, C.c_uint32]
+        L.atz_set_containers.argtypes = [C.c_void_p, C.c_uint32]
+        L.atz_container_anchors.argtypes = [C.c_void_p, C.c_char_p, u64, C.c_uint32, C.POINTER(C.POINTER(u64)),
+                                            C.POINTER(u64)]
         L.atz_deflate_bound.restype = u64
         L.atz_deflate_bound.argtypes = [u64, C.c_int, C.c_int]
         L.atz_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, u64, C.c_int, C.c_int, C.POINTER(u8p),
@@ -148,19 +173,26 @@ class Context:
     """One libatz_accel context (one GPU).  Mirrors the reference's programOptions (ATZData.h:7-35)."""
 
     def __init__(self, recomp_tresh=128, sizediff_tresh=128, shortcut_len=512, mismatch_tol=2,
-                 chunksize=524288, brute_window=False, device=-1, strategies=None):
+                 chunksize=524288, brute_window=False, device=-1, strategies=None, containers=None):
         """strategies: names of zlib strategies ("filtered", "rle", "huffman") to try on the streams the
         reference walk leaves unrecorded (an extension, off by default; None reads ATZ_STRATEGIES, a
-        comma-separated list, as the CLI does)."""
+        comma-separated list, as the CLI does).
+        containers: "zip", "gzip": also look for the raw deflate bodies of ZIP entries and gzip members (an
+        extension, off by default; None reads ATZ_CONTAINERS, a comma-separated list, as the CLI does)."""
         L = lib()
         self.o = Opts(recomp_tresh, sizediff_tresh, shortcut_len, mismatch_tol, chunksize, int(brute_window), device)
         if strategies is None:
             strategies = os.environ.get("ATZ_STRATEGIES", "")
         mask = strategy_mask(strategies)
+        if containers is None:
+            containers = os.environ.get("ATZ_CONTAINERS", "")
+        cmask = container_mask(containers)
         self.h = C.c_void_p()
         _check(L.atz_open(C.byref(self.h), C.byref(self.o)))
         if mask:
             _check(L.atz_set_strategies(self.h, mask))
+        if cmask:
+            _check(L.atz_set_containers(self.h, cmask))
 
     def close(self):
         if self.h:
@@ -270,9 +302,19 @@ class Context:
         self._cands = None
         return out, diffs
 
-    def deflate(self, data, clevel, window, memlevel, strategy=0):
-        if strategy:
-            return self.deflate_batch(data, [(0, len(data), clevel, window, memlevel, strategy)])[0]
+    def container_anchors(self, data, mask):
+        """The anchor kernel's list for `data` (parity/debug): [(position, kind)], kind 0 ZIP, 1 gzip."""
+        L = lib()
+        p = C.POINTER(u64)()
+        n = u64(0)
+        _check(L.atz_container_anchors(self.h, data, len(data), mask, C.byref(p), C.byref(n)))
+        out = [(p[i] >> 5, p[i] & 31) for i in range(n.value)]
+        L.atz_free(p)
+        return out
+
+    def deflate(self, data, clevel, window, memlevel, strategy=0, raw=False):
+        if strategy or raw:
+            return self.deflate_batch(data, [(0, len(data), clevel, window, memlevel, strategy, raw)])[0]
         L = lib()
         cap = L.atz_deflate_bound(len(data), 10, 1) + 1024
         out = C.create_string_buffer(cap)
@@ -281,13 +323,15 @@ class Context:
         return out.raw[:n.value]
 
     def deflate_batch(self, buf, items):
-        """items: list of (offset, length, clevel, window, memlevel[, strategy]) over `buf`; returns list of bytes."""
+        """items: list of (offset, length, clevel, window, memlevel[, strategy[, raw]]) over `buf`; returns list of
+        bytes.  raw: the deflate body alone (no zlib header, no Adler-32 trailer)."""
         L = lib()
         k = len(items)
         offs = (u64 * max(k, 1))(*[it[0] for it in items])
         lens = (u64 * max(k, 1))(*[it[1] for it in items])
-        ex = any(len(it) > 5 and it[5] for it in items)
-        prm = (C.c_uint32 * max(k, 1))(*[((it[5] << 24) if len(it) > 5 else 0) | (it[2] << 16) | (it[3] << 8) | it[4]
+        ex = any((len(it) > 5 and it[5]) or (len(it) > 6 and it[6]) for it in items)
+        prm = (C.c_uint32 * max(k, 1))(*[((1 << 28) if len(it) > 6 and it[6] else 0) |
+                                         ((it[5] << 24) if len(it) > 5 else 0) | (it[2] << 16) | (it[3] << 8) | it[4]
                                          for it in items])
         caps = [L.atz_deflate_bound(it[1], 10, 1) + 64 for it in items]
         oo, tot = [], 0

@@ -392,6 +392,7 @@ void prange(std::vector<uint32_t>& l, int cmin, int cmax, int wmin, int wmax, in
 }
 // tryParamsFastest/Fast/Default/Best (main.cpp:487-560)
 void list_a(std::vector<uint32_t>& l, int type) {
+  if (type >= 24) return;   // a raw record (the container extension): the reference walk leaves it alone
   int w = 10 + type / 4;
   switch (type % 4) {
     case 0: l.push_back(pk(0, w, 8)); l.push_back(pk(1, w, 8)); l.push_back(pk(1, w, 9));
@@ -406,6 +407,7 @@ void list_a(std::vector<uint32_t>& l, int type) {
 }
 // brute-window continuation (main.cpp:590-601)
 void list_b(std::vector<uint32_t>& l, int type) {
+  if (type >= 24) return;
   int w = 10 + type / 4;
   if (w == 10) prange(l, 1, 9, 11, 15, 1, 9);
   else if (w == 15) prange(l, 1, 9, 10, 14, 1, 9);
@@ -414,9 +416,9 @@ void list_b(std::vector<uint32_t>& l, int type) {
 
 // The trial lists depend only on the header type (24) and the phase: built once, shared by streams.
 const std::vector<uint32_t>& trial_list(int type, bool brute) {
-  static const std::array<std::array<std::vector<uint32_t>, 24>, 2> L = [] {
-    std::array<std::array<std::vector<uint32_t>, 24>, 2> t;
-    for (int ty = 0; ty < 24; ty++) { list_a(t[0][ty], ty); list_b(t[1][ty], ty); }
+  static const std::array<std::array<std::vector<uint32_t>, 27>, 2> L = [] {   // 24..26: raw records, empty
+    std::array<std::array<std::vector<uint32_t>, 27>, 2> t;
+    for (int ty = 0; ty < 27; ty++) { list_a(t[0][ty], ty); list_b(t[1][ty], ty); }
     return t;
   }();
   return L[brute ? 1 : 0][type];
@@ -666,6 +668,9 @@ struct atz_ctx {
   // opt-in strategy trials (atz_set_strategies): bit k = zlib strategy k (1 Z_FILTERED, 2 Z_HUFFMAN_ONLY,
   // 3 Z_RLE) is tried on the streams the reference walk leaves unrecorded; 0: off
   uint32_t strat_mask = 0;
+  // opt-in container anchors (atz_set_containers): bit 0 ZIP local file headers, bit 1 gzip members -- raw
+  // deflate bodies behind them become records of type 24 + hint, which only raw_pass walks; 0: off
+  uint32_t cont_mask = 0;
   // atz_sweep reports every stream's best ident, c, w, m as the reference computes them; the precompress
   // paths only need what the ATZ1 holds, so they let trials stop once they cannot make their stream
   // recompressible (elig_floor)
@@ -831,7 +836,7 @@ static bool timing_on() { return timing_level() >= 1; }
 
 static int run_inflate_jobs(atz_ctx* c, const uint8_t* d_in, uint8_t* d_out, const std::vector<InfJob>& jobs,
                             std::vector<InfRes>& res, uint64_t arena_cap = 0, bool full_ring = false,
-                            bool arena_reset = true) {
+                            bool arena_reset = true, bool raw = false) {
   res.resize(jobs.size());
   if (jobs.empty()) return 0;
   auto ti0 = std::chrono::steady_clock::now();
@@ -848,14 +853,11 @@ static int run_inflate_jobs(atz_ctx* c, const uint8_t* d_in, uint8_t* d_out, con
   bool small = !full_ring;
   for (const InfJob& jb : jobs) small = small && jb.out_off != NO_OUT;
   kbeg(c, 1);
-  if (small)
-    hipLaunchKernelGGL(k_inflate<INF_RING_SMALL>, dim3(n), dim3(64), 0, c->st, d_in,
-                       d_out, c->d_jobs.as<InfJob>(), c->d_res.as<InfRes>(), n, c->d_arena.as<uint8_t>(),
-                       c->d_arena_used.as<unsigned long long>(), arena_cap);
-  else
-    hipLaunchKernelGGL(k_inflate<INF_RING_FULL>, dim3(n), dim3(64), 0, c->st, d_in,
-                       d_out, c->d_jobs.as<InfJob>(), c->d_res.as<InfRes>(), n, c->d_arena.as<uint8_t>(),
-                       c->d_arena_used.as<unsigned long long>(), arena_cap);
+  // raw: deflate bodies without the zlib wrapper (the container extension's candidates and records)
+  auto kern = small ? (raw ? k_inflate<INF_RING_SMALL, true> : k_inflate<INF_RING_SMALL>)
+                    : (raw ? k_inflate<INF_RING_FULL, true> : k_inflate<INF_RING_FULL>);
+  hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, c->st, d_in, d_out, c->d_jobs.as<InfJob>(), c->d_res.as<InfRes>(), n,
+                     c->d_arena.as<uint8_t>(), c->d_arena_used.as<unsigned long long>(), arena_cap);
   kend(c);
   KCHECK("k_inflate");
   const double ti_launch = ms_since(ti0);
@@ -878,7 +880,7 @@ static int run_inflate_jobs(atz_ctx* c, const uint8_t* d_in, uint8_t* d_out, con
       }
     if (!rj.empty()) {
       std::vector<InfRes> rr;
-      if (int r = run_inflate_jobs(c, d_in, d_out, rj, rr, 0, true)) return r;
+      if (int r = run_inflate_jobs(c, d_in, d_out, rj, rr, 0, true, true, raw)) return r;
       for (size_t q = 0; q < ri.size(); q++) res[ri[q]] = rr[q];
       c->stats.n_inflate_retries += rj.size();
     }
@@ -1336,14 +1338,172 @@ static int scan_piece(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, ScanS
   return scan_replay(c, h, S, ja, jb);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Opt-in container anchors (atz_set_containers).  ZIP entries and gzip members hold
+// raw deflate bodies, which no zlib header announces.  k_anchors_ordered lists the fixed headers of both
+// containers in file order; the host parses their variable parts; one raw k_inflate launch decodes the
+// bodies; what the container's own size fields confirm becomes a record of type 24 + hint, merged into
+// the reference's records (which are made first and never change).
+struct RawCand {
+  uint64_t p, d, limit;   // anchor, first body byte, bytes offered to the decoder
+  int kind, hint;         // 0 ZIP / 1 gzip; 0 none, 1 fast, 2 max
+  bool know_c, know_u;    // ZIP: the header states the compressed / the uncompressed size
+  uint64_t csize, usize;
+};
+
+// the anchors of the file, ascending: position << 5 | kind (count pass, host prefix, write pass)
+static int anchors_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint32_t mask, std::vector<uint64_t>& out) {
+  out.clear();
+  if (!mask || !F) return 0;
+  const uint64_t nb = std::max<uint64_t>(1, std::min<uint64_t>(8192, (F + 65535) / 65536));
+  const uint64_t seg = ((F + nb - 1) / nb + 4095) & ~4095ull;
+  if (int r = c->d_cnt.reserve(nb * 4 + 64)) return r;
+  if (int r = c->d_hbase.reserve(nb * 8 + 64)) return r;
+  const auto t0 = std::chrono::steady_clock::now();
+  const double other0 = c->stats.k_other_ms;
+  kbeg(c, 3);
+  hipLaunchKernelGGL(k_anchors_ordered, dim3((uint32_t)nb), dim3(256), 0, c->st, d_file, F, seg, mask,
+                     c->d_cnt.as<uint32_t>(), nullptr, nullptr, 0);
+  kend(c);
+  KCHECK("k_anchors_ordered");
+  std::vector<uint32_t> cnt(nb);
+  HIPCHK(hipMemcpyAsync(cnt.data(), c->d_cnt.p, nb * 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  std::vector<uint64_t> hb(nb);
+  uint64_t na = 0;
+  for (uint64_t b = 0; b < nb; b++) { hb[b] = na; na += cnt[b]; }
+  if (na) {
+    if (int r = upload(c, c->d_hbase, hb.data(), nb * 8)) return r;
+    if (int r = c->d_pos.reserve(na * 8 + 64)) return r;
+    kbeg(c, 3);
+    hipLaunchKernelGGL(k_anchors_ordered, dim3((uint32_t)nb), dim3(256), 0, c->st, d_file, F, seg, mask, nullptr,
+                       c->d_hbase.as<uint64_t>(), c->d_pos.as<uint64_t>(), 1);
+    kend(c);
+    KCHECK("k_anchors_ordered");
+    out.resize(na);
+    HIPCHK(hipMemcpyAsync(out.data(), c->d_pos.p, na * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+  }
+  kcollect(c);
+  if (timing_on())
+    std::fprintf(stderr, "atz: k_anchors_ordered: %llu anchors, kernels %.3f ms (both passes), host %.2f ms\n",
+                 (unsigned long long)na, c->stats.k_other_ms - other0, ms_since(t0));
+  return 0;
+}
+
+static uint32_t rd2(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+static uint32_t rd4(const uint8_t* p) { return rd2(p) | (rd2(p + 2) << 16); }
+
+// The variable part of each anchor's header, from the host copy: where the body starts, how many bytes
+// the decoder may read, the level hint the container carries.  An anchor whose header runs past the end
+// of the file, or that leaves no byte for a body, is dropped.
+static void raw_candidates(const uint8_t* h, uint64_t n, const std::vector<uint64_t>& anchors, std::vector<RawCand>& out) {
+  out.clear();
+  for (const uint64_t a : anchors) {
+    RawCand r{};
+    r.p = a >> 5; r.kind = (int)(a & 31);
+    const uint8_t* q = h + r.p;
+    if (r.kind == 0) {
+      const uint32_t flag = rd2(q + 6);
+      r.csize = rd4(q + 18); r.usize = rd4(q + 22);
+      r.d = r.p + 30 + rd2(q + 26) + rd2(q + 28);
+      if (r.d >= n) continue;
+      const bool dd = flag & 8;   // sizes follow the body in a data descriptor
+      r.know_c = !dd && r.csize != 0 && r.csize != 0xffffffffu;
+      r.know_u = !dd && r.usize != 0xffffffffu;
+      if (r.know_c && r.csize > n - r.d) continue;
+      r.limit = r.know_c ? r.csize : n - r.d;
+      const uint32_t lv = (flag >> 1) & 3;   // general purpose bits 2-1: 01 maximum, 10 fast, 11 super fast
+      r.hint = lv == 1 ? 2 : lv >= 2 ? 1 : 0;
+    } else {
+      const uint32_t flg = q[3], xfl = q[8];
+      uint64_t at = r.p + 10;
+      bool ok = true;
+      if (flg & 4) {   // FEXTRA
+        if (at + 2 > n) continue;
+        at += 2 + rd2(h + at);
+        ok = at <= n;
+      }
+      for (uint32_t bit = 8; ok && bit <= 16; bit <<= 1)   // FNAME, FCOMMENT: zero-terminated
+        if (flg & bit) {
+          while (at < n && h[at]) at++;
+          ok = at < n;
+          at++;
+        }
+      if (ok && (flg & 2)) { at += 2; ok = at <= n; }   // FHCRC
+      if (!ok || at + 8 >= n) continue;   // (the trailer's 8 bytes follow the body)
+      r.d = at;
+      r.limit = n - at - 8;
+      r.hint = xfl == 2 ? 2 : xfl == 4 ? 1 : 0;
+    }
+    out.push_back(r);
+  }
+}
+
+// The raw records of the file merged into c->recs (the reference's, complete): candidates decoded (outputs
+// kept in the scan's arena, behind the reference candidates'; fresh_arena: the scan ran no job), accepted
+// by the container's own fields, dropped where they meet a reference record, taken greedily in ascending
+// offset.  c->recs keeps its capacity (the sweep's tables are sized for it).
+static int raw_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t arena_cap, bool fresh_arena,
+                     const std::vector<RawCand>& cands) {
+  if (cands.empty()) return 0;
+  auto tm_ = std::chrono::steady_clock::now();
+  std::vector<InfJob> jobs(cands.size());
+  for (size_t k = 0; k < cands.size(); k++) jobs[k] = {cands[k].d, cands[k].limit, ARENA_OUT, ARENA_SLOT};
+  std::vector<InfRes> res;
+  if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, arena_cap, false, fresh_arena, true)) return r;
+  std::vector<std::pair<Rec, uint64_t>> acc;   // (record, anchor position)
+  const std::vector<Rec>& ref = c->recs;
+  for (size_t k = 0; k < cands.size(); k++) {
+    const RawCand& a = cands[k];
+    const InfRes& r = res[k];
+    if (r.status != INF_END || r.produced < 1 || r.produced >= (1ull << 31)) continue;
+    if (a.kind == 0) {
+      if (a.know_c && r.consumed != a.csize) continue;
+      if (a.know_u && r.produced != a.usize) continue;
+    } else if (rd4(h + a.d + r.consumed + 4) != (uint32_t)r.produced) {   // ISIZE
+      continue;
+    }
+    // a reference record that meets [d, d + consumed): the raw one is dropped
+    const uint64_t lo = a.d, hi = a.d + r.consumed;
+    const auto it = std::lower_bound(ref.begin(), ref.end(), hi, [](const Rec& x, uint64_t v) { return x.offset < v; });
+    if (it != ref.begin() && (it - 1)->offset + (it - 1)->comp_len > lo) continue;
+    Rec rec{a.d, r.consumed, r.produced, 24 + a.hint, 0, r.arena_off};
+    acc.push_back({rec, a.p});
+  }
+  std::stable_sort(acc.begin(), acc.end(), [](const auto& x, const auto& y) {
+    return x.first.offset != y.first.offset ? x.first.offset < y.first.offset : x.second < y.second;
+  });
+  std::vector<Rec> merged;
+  merged.reserve(ref.size() + acc.size());
+  size_t i = 0;
+  uint64_t end = 0;
+  for (const auto& e : acc) {
+    if (e.first.offset < end) continue;   // starts inside the raw record kept before it
+    end = e.first.offset + e.first.comp_len;
+    while (i < ref.size() && ref[i].offset < e.first.offset) merged.push_back(ref[i++]);
+    merged.push_back(e.first);
+  }
+  while (i < ref.size()) merged.push_back(ref[i++]);
+  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
+  c->recs.assign(merged.begin(), merged.end());
+  TMARK("scan: raw candidates");
+  return 0;
+}
+
 // Every record, one piece.  (atz_scan; precompress_dev scans piece by piece while the sweep runs)
 static int scan_impl(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t F) {
   auto t0 = std::chrono::steady_clock::now();
   c->recs.clear();
   ScanState S;
   if (int r = scan_plan(c, h, d_file, F, S)) return r;
-  c->recs.reserve(S.max_records());
+  std::vector<uint64_t> anchors;
+  std::vector<RawCand> rc;
+  if (int r = anchors_dev(c, d_file, F, c->cont_mask, anchors)) return r;
+  raw_candidates(h, F, anchors, rc);
+  c->recs.reserve(S.max_records() + rc.size());
   if (int r = scan_piece(c, h, d_file, S, 0, (uint32_t)S.chunks.size())) return r;
+  if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), rc)) return r;
   c->stats.scan_ms = ms_since(t0);
   return 0;
 }
@@ -1368,8 +1528,8 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
   // Streams whose scan decode kept its full output in the arena are copied; the others are
   // inflated again from the file with their exact length (doInflate, main.cpp:461-486) -- the
   // same bytes from the same offset, so both give the same result.
-  std::vector<InfJob> jobs;
-  std::vector<size_t> job_rec;
+  std::vector<InfJob> jobs, raw_jobs;
+  std::vector<size_t> job_rec, raw_rec;
   std::vector<Seg> segs;
   for (size_t s = r0; s < r1; s++) {
     const Rec& r = c->recs[s];
@@ -1379,8 +1539,8 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
     } else {
       InfJob jb;
       jb.in_off = r.offset; jb.in_len = r.comp_len; jb.out_off = loc[s - r0]; jb.out_cap = r.infl_len;
-      jobs.push_back(jb);
-      job_rec.push_back(s);
+      (r.type >= 24 ? raw_jobs : jobs).push_back(jb);
+      (r.type >= 24 ? raw_rec : job_rec).push_back(s);
     }
   }
   if (!segs.empty()) {
@@ -1396,6 +1556,13 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
   TMARK("records: arena gather launch");
   std::vector<InfRes> res;
   if (int r = run_inflate_jobs(c, d_file, slab.as<uint8_t>(), jobs, res)) return r;
+  if (!raw_jobs.empty()) {   // raw records (the container extension): the decoder without HEAD and CHECK
+    std::vector<InfRes> rres;
+    if (int r = run_inflate_jobs(c, d_file, slab.as<uint8_t>(), raw_jobs, rres, 0, false, true, true)) return r;
+    jobs.insert(jobs.end(), raw_jobs.begin(), raw_jobs.end());
+    job_rec.insert(job_rec.end(), raw_rec.begin(), raw_rec.end());
+    res.insert(res.end(), rres.begin(), rres.end());
+  }
   if (timing_on()) {
     uint64_t mx = 0, tot = 0;
     for (const InfJob& jb : jobs) { mx = std::max(mx, jb.in_len); tot += jb.in_len; }
@@ -1413,6 +1580,7 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
     // Adler-32 of the inflated bytes = the verified trailer (atz_sweep: saved by atz_scan, whose
     // host buffer the caller need not keep alive)
     const uint64_t e = c->recs[s].offset + c->recs[s].comp_len;
+    if (c->recs[s].type >= 24) { c->adler[s] = 0; continue; }   // a raw body has no trailer (TM_RAW trials write none)
     c->adler[s] = c->hfile ? ((uint32_t)c->hfile[e - 4] << 24) | ((uint32_t)c->hfile[e - 3] << 16) |
                                  ((uint32_t)c->hfile[e - 2] << 8) | c->hfile[e - 1]
                            : c->scan_trailer[s];
@@ -3059,7 +3227,11 @@ static int sweep_publish(atz_ctx* c, SweepRun& R, size_t r0, size_t r1) {
     auto& Q = c->sched;
     std::lock_guard<std::mutex> lk(Q.mu);
     // interleaved over the pipes by global index: every pipe gets the same mix of classes and sizes
-    for (size_t s = r0; s < r1; s++) { Q.q[s % R.np].push_back((uint32_t)s); Q.unfinished[s % R.np]++; }
+    // (a raw record has no reference walk: done at once; raw_pass walks it after the sweep)
+    for (size_t s = r0; s < r1; s++) {
+      if (c->recs[s].type >= 24) { (*R.ss)[s].phase = 2; continue; }
+      Q.q[s % R.np].push_back((uint32_t)s); Q.unfinished[s % R.np]++;
+    }
     Q.published = r1;
     Q.cv.notify_all();
   }
@@ -3218,6 +3390,7 @@ struct SweepGuard {
 // (Z/deflate.c:738-750): 0 for strategy >= Z_HUFFMAN_ONLY, else by level -- at the header's window,
 // memLevels 8, 9, 7..1, levels descending within a memLevel.  Entries: (strategy<<24)|(c<<16)|(w<<8)|m.
 static void strategy_list(std::vector<uint32_t>& l, int type, uint32_t mask) {
+  if (type >= 24) return;   // raw records take no strategy trials
   const int w = 10 + type / 4;
   static const int mo[9] = {8, 9, 7, 6, 5, 4, 3, 2, 1};
   auto add = [&](uint32_t strat, int chi, int clo) {
@@ -3236,8 +3409,9 @@ static void strategy_list(std::vector<uint32_t>& l, int type, uint32_t mask) {
 // One round per list position on pipe 0, the streams of a round in batches within the scratch budget (each
 // batch builds the bucket tables its filtered trials read, as deflate_dev does).  A stream the pass
 // records gets clevel = strategy << 4 | level; the others keep what the reference walk left.
-static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
-  if (!c->strat_mask) return 0;
+// raw: the same pass over the container extension's records (raw_list; TM_RAW trials), see raw_pass.
+static void raw_list(std::vector<uint32_t>& l, int type);
+static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss, bool raw) {
   const auto t0 = std::chrono::steady_clock::now();
   const size_t n = ss.size();
   struct Ext {
@@ -3253,7 +3427,8 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
   size_t longest = 0;
   for (size_t s = 0; s < n; s++) {
     if (ss[s].recomp || c->recs[s].infl_len >= (1ull << 31)) continue;
-    strategy_list(ex[s].list, c->recs[s].type, c->strat_mask);
+    if (raw) raw_list(ex[s].list, c->recs[s].type);
+    else strategy_list(ex[s].list, c->recs[s].type, c->strat_mask);
     if (ex[s].list.empty()) continue;
     todo.push_back((uint32_t)s);
     longest = std::max(longest, ex[s].list.size());
@@ -3286,15 +3461,15 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
       std::vector<std::pair<uint32_t, int>> need;
       for (size_t a = a0; a < a1; a++) {
         const uint32_t q = ex[act[a]].list[j];
-        if ((q >> 24) == 1) need.push_back({act[a], (int)(q & 0xff)});
+        if (raw ? ((q >> 16) & 0xff) > 0 : (q >> 24) == 1) need.push_back({act[a], (int)(q & 0xff)});
       }
       if (int r = private_chains(c, p, need)) return r;
       TrialBatch B;   // never saves, replays or stands for a duplicate
       for (size_t a = a0; a < a1; a++) {
         const uint32_t s = act[a], q = ex[s].list[j];
         const int m = (int)(q & 0xff);
-        const auto at = B.add(p, s, c->recs[s].infl_len, (int)((q >> 16) & 0xff), (int)((q >> 8) & 0xff), m, q >> 24, 0,
-                              std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len)));
+        const auto at = B.add(p, s, c->recs[s].infl_len, (int)((q >> 16) & 0xff), (int)((q >> 8) & 0xff), m, (q >> 24) & 3,
+                              raw ? TM_RAW : 0, std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len)));
         if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m];
       }
       if (int r = B.reserve(p)) return r;
@@ -3337,7 +3512,7 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
     const uint64_t C = c->recs[s].comp_len;
     if (!(e.ident > 0 && C - e.ident <= c->o.recomp_tresh)) continue;   // main.cpp:454
     StreamState& st = ss[s];
-    st.c = (uint8_t)(((e.best >> 24) << 4) | ((e.best >> 16) & 0xff));
+    st.c = (uint8_t)((((e.best >> 28) & 1u) << 6) | (((e.best >> 24) & 3u) << 4) | ((e.best >> 16) & 0xff));
     st.w = (uint8_t)((e.best >> 8) & 0xff); st.m = (uint8_t)(e.best & 0xff);
     st.ident = e.ident;
     st.rawdiff.swap(e.rawdiff); st.diffval.swap(e.diffval);
@@ -3352,9 +3527,30 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
   t.k_match_ms += q.k_match_ms - before.k_match_ms; t.k_match_launches += q.k_match_launches - before.k_match_launches;
   t.k_other_ms += q.k_other_ms - before.k_other_ms;
   t.sweep_ms += ms_since(t0);
-  if (timing_on()) std::fprintf(stderr, "atz: strategy pass: %zu streams, %llu trials  %9.2f ms\n", todo.size(),
-                                (unsigned long long)tally.ntr, ms_since(t0));
+  if (timing_on()) std::fprintf(stderr, "atz: %s pass: %zu streams, %llu trials  %9.2f ms\n", raw ? "raw" : "strategy",
+                                todo.size(), (unsigned long long)tally.ntr, ms_since(t0));
   return 0;
+}
+static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
+  return c->strat_mask ? ext_pass(c, d_file, ss, false) : 0;
+}
+
+// The raw walk (the container extension): a record of type 24 + hint is a raw deflate body
+// of C = comp_len bytes behind a ZIP or gzip header.  Its candidates: window 15 (what ZIP and gzip writers
+// use; --brute-window does not widen it), the default strategy, memLevels 8, 9, 7..1, and inside a
+// memLevel the levels in the order its container's hint suggests -- 90 entries, raw << 28 | c << 16 |
+// 15 << 8 | m.  The rule is strategy_pass's, on the body: a recorded one gets clevel = 1 << 6 | level.
+static void raw_list(std::vector<uint32_t>& l, int type) {
+  if (type < 24 || type > 26) return;
+  static const int mo[9] = {8, 9, 7, 6, 5, 4, 3, 2, 1};
+  static const int lo[3][10] = {{6, 9, 1, 5, 7, 8, 4, 3, 2, 0},    // no hint
+                                {1, 2, 3, 4, 5, 6, 7, 8, 9, 0},    // fast
+                                {9, 8, 7, 6, 5, 4, 3, 2, 1, 0}};   // max
+  for (int m : mo)
+    for (int cl : lo[type - 24]) l.push_back((1u << 28) | pk(cl, 15, m));
+}
+static int raw_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
+  return c->cont_mask ? ext_pass(c, d_file, ss, true) : 0;
 }
 
 // the sweep of every record of the context (atz_sweep)
@@ -3365,7 +3561,8 @@ static int sweep_impl(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState
   if (int r = sweep_begin(c, d_file, ss, n, R)) return r;
   if (int r = sweep_publish(c, R, 0, n)) return r;
   if (int r = sweep_finish(c, R)) return r;
-  return strategy_pass(c, d_file, ss);
+  if (int r = strategy_pass(c, d_file, ss)) return r;
+  return raw_pass(c, d_file, ss);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3435,7 +3632,8 @@ static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<
   return 0;
 }
 
-// version 2 (the strategy extension): some descriptor's clevel byte is strategy << 4 | level
+// version 2 (the strategy extension): some descriptor's clevel byte is strategy << 4 | level;
+// version 3 (the container extension): some descriptor's is raw << 6 | strategy << 4 | level
 static void atz_header(std::vector<uint8_t>& meta, uint64_t F, uint64_t nrec, uint8_t version = 1) {
   const uint8_t h[4] = {'A', 'T', 'Z', version};
   meta.insert(meta.end(), h, h + 4);
@@ -3449,10 +3647,10 @@ static int write_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::
   std::vector<Seg> segs;
   const size_t n = c->recs.size();
   uint64_t nrec = 0;
-  uint8_t version = 1;   // ATZ1 unless a recorded stream carries a strategy
+  uint8_t version = 1;   // ATZ1 unless a recorded stream carries a strategy (2) or is raw (3)
   for (size_t s = 0; s < n; s++) {
     nrec += ss[s].recomp;
-    if (ss[s].recomp && (ss[s].c >> 4)) version = 2;
+    if (ss[s].recomp && (ss[s].c >> 4)) version = std::max<uint8_t>(version, (ss[s].c & 0x40) ? 3 : 2);
   }
   atz_header(meta, F, nrec, version);
   segs.push_back({0, 0, 0, 0, meta.size()});
@@ -3492,7 +3690,14 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   if (!c->scan_keep) c->scan_keep = std::make_shared<ScanState>();
   ScanState& S = *c->scan_keep;
   if (int r = scan_plan(c, h, d_file, F, S)) return r;
-  const size_t n_max = S.max_records();
+  // the container extension's candidates (none without a mask): the sweep's tables have room for them
+  std::vector<RawCand> raw_cands;
+  if (c->cont_mask) {
+    std::vector<uint64_t> anchors;
+    if (int r = anchors_dev(c, d_file, F, c->cont_mask, anchors)) return r;
+    raw_candidates(h, F, anchors, raw_cands);
+  }
+  const size_t n_max = S.max_records() + raw_cands.size();
   c->recs.reserve(n_max);
   std::vector<StreamState>& ss = c->ss_keep;
   SweepRun R;
@@ -3518,7 +3723,9 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   });
   struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join_begin{t_begin};
   double scan_busy = ms_since(t0);
-  if (P == 1 && spec_cont_on()) {
+  // (with a container mask the raw records need the reference's final ones: scan, merge, then sweep)
+  const bool spec = P == 1 && spec_cont_on() && !c->cont_mask;
+  if (spec) {
     // The first continuations of pending streams (each a decode of the stream from its header through
     // the chunk boundary) are latency-bound: one small launch, 15-30 ms.  The records do not wait for
     // it: they are replayed as if every continuation fails -- the refill repeats the chunk's last
@@ -3577,11 +3784,12 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
     TMARK("scan: continuations checked");
     scan_busy += ms_since(t0) - scan_busy;
   }
-  for (uint32_t p = 0; p < P && !(P == 1 && spec_cont_on()); p++) {
+  for (uint32_t p = 0; p < P && !spec; p++) {
     auto tp = std::chrono::steady_clock::now();
     const uint32_t ja = (uint32_t)((uint64_t)nch * p / P), jb = (uint32_t)((uint64_t)nch * (p + 1) / P);
     const size_t r0 = c->recs.size();
     if (int r = scan_piece(c, h, d_file, S, ja, jb)) return r;
+    if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), raw_cands)) return r;
     if (p == 0) {
       t_begin.join();
       if (rc_begin) return rc_begin;
@@ -3594,6 +3802,7 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   c->stats.scan_ms = scan_busy;   // the scan thread's own time (the sweep runs beside it)
   if (int r = sweep_finish(c, R)) return r;
   if (int r = strategy_pass(c, d_file, ss)) return r;
+  if (int r = raw_pass(c, d_file, ss)) return r;
   c->infl_off.resize(c->recs.size());
   c->adler.resize(c->recs.size());
   if (int r = write_impl(c, d_file, F, ss, atz_len)) return r;
@@ -3652,15 +3861,15 @@ static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std:
     }
     c->chain_off.assign(n, {});
     std::vector<std::pair<uint32_t, int>> need;
-    // (params carry a strategy in bits 24-25: Z_RLE and Z_HUFFMAN_ONLY read no bucket tables)
+    // (params carry a strategy in bits 24-25: Z_RLE and Z_HUFFMAN_ONLY read no bucket tables; bit 28: raw output)
     for (size_t s = s0; s < s1; s++)
-      if (((params[s] >> 16) & 0xff) > 0 && (params[s] >> 24) < 2) need.push_back({(uint32_t)s, (int)(params[s] & 0xff)});
+      if (((params[s] >> 16) & 0xff) > 0 && ((params[s] >> 24) & 3) < 2) need.push_back({(uint32_t)s, (int)(params[s] & 0xff)});
     if (int r = private_chains(c, p, need)) return r;
     TrialBatch B;
     for (size_t s = s0; s < s1; s++) {
       const int m = (int)(params[s] & 0xff);
       const auto at = B.add(p, (uint32_t)s, len[s], (int)((params[s] >> 16) & 0xff), (int)((params[s] >> 8) & 0xff), m,
-                            params[s] >> 24, TM_FULL, 0);
+                            (params[s] >> 24) & 3, (uint8_t)(TM_FULL | ((params[s] >> 28) & 1u ? TM_RAW : 0)), 0);
       if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m];
     }
     if (int r = B.reserve(p)) return r;
@@ -3727,8 +3936,9 @@ struct AtzDesc { uint64_t off, cl, il, nd, fd, dpos, ipos; uint8_t c, w, m; };
 // bytes actually left before anything is sized from it (subtraction-only checks: no sum can wrap)
 static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, uint64_t& origlen, uint64_t& residue) {
   // version 2: the strategy extension's files (same layout; clevel = strategy << 4 | level)
-  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || (atz[3] != 1 && atz[3] != 2)) return ATZ_E_FORMAT;   // main.cpp:1018-1021
-  const bool v2 = atz[3] == 2;
+  // version 3: the container extension's (clevel = raw << 6 | strategy << 4 | level)
+  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 3) return ATZ_E_FORMAT;   // main.cpp:1018-1021
+  const bool v2 = atz[3] == 2, v3 = atz[3] == 3;
   if (rd8(atz + 4) != n) return ATZ_E_FORMAT;                              // main.cpp:1022-1025
   origlen = rd8(atz + 12);
   const uint64_t nstrms = rd8(atz + 20);
@@ -3759,7 +3969,10 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
       x.fd = 0; x.dpos = 0; x.ipos = lastos + 35;
       lastos = x.ipos + x.il;
     }
-    if (v2) {   // Z_HUFFMAN_ONLY and Z_RLE have no level 0
+    if (v3) {
+      const uint32_t sg = (x.c >> 4) & 3u;
+      if ((x.c & 0x80) || (x.c & 15) > 9 || sg > 3 || (sg >= 2 && (x.c & 15) < 1)) return ATZ_E_REF_ABORT;
+    } else if (v2) {   // Z_HUFFMAN_ONLY and Z_RLE have no level 0
       if ((x.c & 15) > 9 || (x.c >> 4) > 3 || ((x.c >> 4) >= 2 && (x.c & 15) < 1)) return ATZ_E_REF_ABORT;
     } else if (x.c > 9) return ATZ_E_REF_ABORT;
     if (x.w < 8 || x.w > 15 || x.m < 1 || x.m > 9) return ATZ_E_REF_ABORT;
@@ -3820,7 +4033,8 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
       addr[j] = (uint64_t)(uintptr_t)slab.p + loc[j];
       len[j] = d[j].il;
       const int w = d[j].w == 8 ? 9 : d[j].w;
-      params[j] = ((uint32_t)(d[j].c >> 4) << 24) | ((uint32_t)(d[j].c & 15) << 16) | ((uint32_t)w << 8) | d[j].m;
+      params[j] = ((uint32_t)((d[j].c >> 6) & 1) << 28) | ((uint32_t)((d[j].c >> 4) & 3) << 24) |
+                  ((uint32_t)(d[j].c & 15) << 16) | ((uint32_t)w << 8) | d[j].m;
     }
     if (!segs.empty())
       if (int r = gather_segments(c, d_atz, meta, segs, slab.as<uint8_t>())) return r;
@@ -4376,7 +4590,8 @@ int atz_deflate(atz_ctx_t* c, const uint8_t* in, uint64_t in_len, int clevel, in
   });
 }
 
-// ex: params carry zlib's strategy in bits 24-31 (atz_deflate_batch_ex); else bits 16-31 are the level
+// ex: params carry zlib's strategy in bits 24-27 and the raw flag in bit 28 (atz_deflate_batch_ex); else
+// bits 16-31 are the level
 static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
                              const uint32_t* params, uint64_t n, uint8_t* out, const uint64_t* out_offs,
                              const uint64_t* out_caps, uint64_t* out_lens, bool ex) {
@@ -4387,13 +4602,14 @@ static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, con
     std::vector<uint32_t> ps(n);
     for (uint64_t k = 0; k < n; k++) {
       if (offs[k] + lens[k] > len) return ATZ_E_ARG;
-      const int sg = ex ? (int)(params[k] >> 24) : 0;
+      const uint32_t raw = ex ? (params[k] >> 28) & 1u : 0u;   // no zlib header, no Adler-32 trailer
+      const int sg = ex ? (int)((params[k] >> 24) & ~16u) : 0;
       int cl = (int)(ex ? (params[k] >> 16) & 0xff : params[k] >> 16), w = (int)((params[k] >> 8) & 0xff), m = (int)(params[k] & 0xff);
       if (cl < 0 || cl > 9 || w < 8 || w > 15 || m < 1 || m > 9) return ATZ_E_ARG;
       if (sg > 3 || (sg >= 2 && cl < 1)) return ATZ_E_ARG;   // Z_FIXED is not supported; Z_RLE / Z_HUFFMAN_ONLY have no level 0
       if (w == 8) w = 9;
       ins[k] = {buf + offs[k], lens[k]};
-      ps[k] = ((uint32_t)sg << 24) | ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
+      ps[k] = (raw << 28) | ((uint32_t)sg << 24) | ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
     }
     std::vector<std::vector<uint8_t>> outs;
     if (int r = deflate_many(c, ins, ps, outs)) return r;
@@ -4424,6 +4640,29 @@ int atz_set_strategies(atz_ctx_t* c, uint32_t mask) {
   return ATZ_OK;
 }
 
+int atz_set_containers(atz_ctx_t* c, uint32_t mask) {
+  if (!c || (mask & ~3u)) return ATZ_E_ARG;   // bit 0: ZIP local file headers, bit 1: gzip members
+  c->cont_mask = mask;
+  c->scan_valid = false;
+  return ATZ_OK;
+}
+
+int atz_container_anchors(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint32_t mask, uint64_t** out, uint64_t* n) {
+  return guarded([&]() -> int {
+    (void)hipGetLastError();
+    if (!c || (!file && len) || !out || !n || (mask & ~3u)) return ATZ_E_ARG;
+    c->scan_valid = false; c->shard.stage = 0;   // d_file is replaced
+    if (int r = upload(c, c->d_file, file, len)) return r;
+    std::vector<uint64_t> a;
+    if (int r = anchors_dev(c, c->d_file.as<uint8_t>(), len, mask, a)) return r;
+    *out = (uint64_t*)std::malloc((a.size() + 1) * 8);
+    if (!*out) return ATZ_E_NOMEM;
+    if (!a.empty()) std::memcpy(*out, a.data(), a.size() * 8);
+    *n = a.size();
+    return ATZ_OK;
+  });
+}
+
 int atz_inflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
                       uint64_t n, uint32_t* status, uint64_t* consumed, uint64_t* produced) {
   return guarded([&]() -> int {
@@ -4450,7 +4689,7 @@ int atz_shard_scan(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, u
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !blob || !blob_len || world < 1 || rank < 0 || rank >= world) return ATZ_E_ARG;
-    if (c->strat_mask) return ATZ_E_ARG;   // the strategy extension has no multi-GPU split
+    if (c->strat_mask || c->cont_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
     dev_mark_call();   // (the peak runs on through atz_shard_sweep, whose stats report it)
     std::vector<uint64_t> b;
     if (int r = shard_scan_impl(c, d_file, h_file, len, rank, world, b)) { c->shard.stage = 0; return r; }
@@ -4468,7 +4707,7 @@ int atz_shard_sweep(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, 
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !piece_len || !recomp_flags || !n_flags || !n_recomp) return ATZ_E_ARG;
-    if (c->strat_mask) return ATZ_E_ARG;
+    if (c->strat_mask || c->cont_mask) return ATZ_E_ARG;
     std::vector<uint8_t> f;
     if (int r = shard_sweep_impl(c, d_file, h_file, len, blobs, blob_lens, world, f, n_recomp)) {
       c->shard.stage = 0;

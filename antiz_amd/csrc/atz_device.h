@@ -49,6 +49,7 @@ struct InfRes {
 // Trial::mode: the flags the trial kernels read (TrialRun's constructor), and nothing else
 enum : uint8_t {
   TM_FULL = 1,        // full output needed (no early exits)
+  TM_RAW = 2,         // raw deflate output: no zlib header and no Adler-32 trailer (the container extension)
   TM_SAVE = 4,        // saves its whole symbol sequence at rp_syms
   TM_REPLAY = 8,      // replays the rp_nsym symbols saved at rp_syms instead of parsing
   TM_CHECKED = 16,    // with TM_REPLAY: only if its own match table equals the one saved at rp_tab (else it parses)

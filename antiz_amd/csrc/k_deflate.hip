@@ -894,6 +894,7 @@ struct BitOut {
   uint64_t pos;      // bytes written
   uint64_t bb;       // pending bits (< 8 after every flush)
   uint32_t bc;
+  uint32_t raw;      // TM_RAW: no Adler-32 trailer (kept here, in the struct's padding, not in a register)
   // comparison against the original
   const GLOBAL uint8_t* orig;
   uint64_t clen;     // C_s
@@ -1940,9 +1941,11 @@ __device__ void trial_flusher(const SweepArgs& A, LDS TrialShared& s, LDS MWPart
     uint32_t st = ~0u;
     if (last) {
       // adler32 trailer and the final gates (main.cpp:632-681), as a single-wave trial ends
-      const uint32_t ad = A.adler[tr.stream];
-      const uint32_t be = ((ad >> 24) & 0xff) | ((ad >> 8) & 0xff00) | ((ad << 8) & 0xff0000) | (ad << 24);
-      put_bits(b, stage, be, 32, lane);
+      if (!uni(b.raw)) {
+        const uint32_t ad = A.adler[tr.stream];
+        const uint32_t be = ((ad >> 24) & 0xff) | ((ad >> 8) & 0xff00) | ((ad << 8) & 0xff0000) | (ad << 24);
+        put_bits(b, stage, be, 32, lane);
+      }
       flush_bits_bytes(b, stage, lane);
       if (uni((uint32_t)b.overflow)) st = TR_OVERFLOW;
       else if (full_needed) st = TR_FULL;
@@ -2040,6 +2043,7 @@ struct TrialRun {
     z.last_lit = 0; z.nsym = 0;
     if (wave == 0) {
       b.out = (GLOBAL uint8_t*)(A.out + tr.out_off); b.cap = tr.out_cap; b.pos = 0; b.bb = 0; b.bc = 0;
+      b.raw = tr.mode & TM_RAW;
       b.orig = (const GLOBAL uint8_t*)(A.file + sd.orig_off); b.clen = sd.comp_len;
       b.shortcut = sd.comp_len > A.o.shortcut_len ? A.o.shortcut_len : 0;
       b.eq_all = 0; b.eq_sc = 0; b.overflow = 0;
@@ -2087,8 +2091,8 @@ struct TrialRun {
     cstart = clock64();
     rtstart = (uint32_t)__builtin_amdgcn_s_memrealtime();
     if (wave == 0) init_block(s.f, lane);
-    // zlib header (Z/deflate.c:738-759)
-    if (wave == 0) {
+    // zlib header (Z/deflate.c:738-759); a TM_RAW trial writes the body alone (wrap = 0)
+    if (wave == 0 && !uni((uint32_t)(tr.mode & TM_RAW))) {
       uint32_t header = (8u + ((uint32_t)(tr.window - 8) << 4)) << 8;
       uint32_t lf = z.level < 2 || KIND >= 3 ? 0 : z.level < 6 ? 1 : z.level == 6 ? 2 : 3;   // strategy >= Z_HUFFMAN_ONLY: 0
       header |= lf << 6;
@@ -2989,9 +2993,11 @@ struct TrialRun {
     saved_flags |= 1;   // every symbol tallied: a saving trial's sequence is complete
     FLUSH(1);
     // adler32 trailer
-    uint32_t ad = A.adler[tr.stream];
-    uint32_t be = ((ad >> 24) & 0xff) | ((ad >> 8) & 0xff00) | ((ad << 8) & 0xff0000) | (ad << 24);
-    put_bits(b, stg, be, 32, lane);   // after the last block: the ring is no longer read
+    if (!uni(b.raw)) {
+      uint32_t ad = A.adler[tr.stream];
+      uint32_t be = ((ad >> 24) & 0xff) | ((ad >> 8) & 0xff00) | ((ad << 8) & 0xff0000) | (ad << 24);
+      put_bits(b, stg, be, 32, lane);   // after the last block: the ring is no longer read
+    }
     flush_bits_bytes(b, stg, lane);
     // final gates (main.cpp:632-681)
     if (b.overflow) state = TR_OVERFLOW;

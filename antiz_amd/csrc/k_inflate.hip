@@ -178,6 +178,87 @@ __global__ __launch_bounds__(256) void k_headers_ordered(const uint8_t* __restri
   if (!write && t == 0) cnt[blockIdx.x] = total;
 }
 
+// Container anchors (the opt-in container extension): the fixed part of a ZIP local file
+// header (kind 0, mask bit 0) or of a gzip member header (kind 1, mask bit 1) starts at p.  Every byte
+// read lies inside the file: the length test comes first.  -1: no anchor.
+__device__ inline int anchor_kind(const uint8_t* __restrict__ f, uint64_t p, uint64_t n, uint32_t mask) {
+  const uint32_t b0 = f[p];
+  if (b0 == 0x50 && (mask & 1u)) {
+    if (p + 30 > n) return -1;
+    if (f[p + 1] != 0x4b || f[p + 2] != 0x03 || f[p + 3] != 0x04) return -1;
+    if (f[p + 8] != 8 || f[p + 9] != 0) return -1;   // method: deflate
+    if (f[p + 6] & 1u) return -1;                    // encrypted
+    return 0;
+  }
+  if (b0 == 0x1f && (mask & 2u)) {
+    if (p + 18 > n) return -1;
+    if (f[p + 1] != 0x8b || f[p + 2] != 0x08) return -1;
+    if (f[p + 3] & 0xe0) return -1;                  // reserved FLG bits
+    return 1;
+  }
+  return -1;
+}
+
+// k_headers_ordered's two passes for the anchors: count mode writes the block's total to cnt[b]; write mode
+// writes (position << 5 | kind) in file order from base[b] on.  A lane tests the 16 positions of its
+// 16-byte load for an anchor's first byte and reads on only behind one.
+__global__ __launch_bounds__(256) void k_anchors_ordered(const uint8_t* __restrict__ f, uint64_t n, uint64_t seg,
+                                                         uint32_t mask, uint32_t* __restrict__ cnt,
+                                                         const uint64_t* __restrict__ base, uint64_t* __restrict__ out,
+                                                         int write) {
+  __shared__ uint32_t wsum[4];
+  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const uint64_t s0 = (uint64_t)blockIdx.x * seg;
+  const uint64_t s1 = s0 + seg < n ? s0 + seg : n;
+  uint64_t o = write ? base[blockIdx.x] : 0;
+  uint32_t total = 0;
+  for (uint64_t sb = s0; sb < s1; sb += 4096) {
+    const uint64_t p = sb + (uint64_t)t * 16;
+    uint32_t hits = 0;
+    if (p < s1) {
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (p + 16 <= n) {
+        v = *reinterpret_cast<const uint4*>(f + p);
+      } else {
+        uint32_t x[4] = {0, 0, 0, 0};
+        for (int k = 0; k < 16; k++)
+          if (p + k < n) x[k >> 2] |= (uint32_t)f[p + k] << (8 * (k & 3));
+        v = make_uint4(x[0], x[1], x[2], x[3]);
+      }
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        const uint32_t x = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w;
+        const uint32_t b = (x >> (8 * (k & 3))) & 0xff;
+        if (((b == 0x50 && (mask & 1u)) || (b == 0x1f && (mask & 2u))) && p + k < s1 &&
+            anchor_kind(f, p + k, n, mask) >= 0)
+          hits |= 1u << k;
+      }
+    }
+    const uint32_t c = __popc(hits);
+    uint32_t incl = c;
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t y = __shfl_up(incl, d, 64);
+      if ((int)lane >= d) incl += y;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint32_t before = 0, step = 0;
+    for (uint32_t k = 0; k < 4; k++) { const uint32_t y = wsum[k]; if (k < w) before += y; step += y; }
+    __syncthreads();
+    if (write) {
+      uint64_t q = o + before + incl - c;
+      while (hits) {
+        const int k = __ffs(hits) - 1;
+        hits &= hits - 1;
+        out[q++] = ((p + k) << 5) | (uint64_t)anchor_kind(f, p + k, n, mask);   // position << 5 | kind
+      }
+    }
+    o += step;
+    total += step;
+  }
+  if (!write && t == 0) cnt[blockIdx.x] = total;
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_inflate: one wavefront per job, everything inlined into the kernel so the decoder state stays
 // in (wave-uniform) SGPRs -- a by-reference state struct crossing a call would live in scratch.
@@ -266,7 +347,9 @@ struct InfShared {
   uint16_t sort[384];
 };
 
-template <uint32_t RING>
+// RAW (the container extension's candidates): a raw deflate body -- no zlib header (HEAD)
+// and no Adler-32 trailer (CHECK); total_in is the position after the final block, rounded up to a byte.
+template <uint32_t RING, bool RAW = false>
 __global__ __launch_bounds__(64, RING == INF_RING_FULL ? 1 : INF_SMALL_WAVES) void k_inflate(const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base,
                                                const InfJob* __restrict__ jobs, InfRes* __restrict__ res,
                                                uint32_t njobs, uint8_t* __restrict__ arena,
@@ -705,13 +788,14 @@ __global__ __launch_bounds__(64, RING == INF_RING_FULL ? 1 : INF_SMALL_WAVES) vo
 
   auto body = [&]() __attribute__((always_inline)) -> int {
     // HEAD (Z/inflate.c:640-685): wrap=1, wbits=15
-    NEEDB(16);
-    const uint32_t cmf = peek(8);
-    const uint32_t flg = (peek(16) >> 8) & 0xff;
+    // (RAW: no header to read; a valid one stands in, so every check folds away)
+    if constexpr (!RAW) NEEDB(16);
+    const uint32_t cmf = RAW ? 0x78u : peek(8);
+    const uint32_t flg = RAW ? 0x9cu : (peek(16) >> 8) & 0xff;
     if (((cmf << 8) + flg) % 31) FAIL(1, pos + 16);
     if ((cmf & 15) != 8) FAIL(2, pos + 16);
     if ((cmf >> 4) + 8 > 15) FAIL(3, pos + 16);
-    drop(16);
+    if constexpr (!RAW) drop(16);
     if (flg & 0x20) { NEEDB(32); FAIL(4, pos + 32); }      // preset dictionary: not a stream end
     int last;
     Huff lh, dh;
@@ -875,6 +959,11 @@ __global__ __launch_bounds__(64, RING == INF_RING_FULL ? 1 : INF_SMALL_WAVES) vo
     // CHECK (Z/inflate.c:1174-1195)
     const uint32_t al = (uint32_t)((8 - (pos & 7)) & 7);
     drop(al);
+    if constexpr (RAW) {   // wrap = 0: no trailer
+      stage_flush();
+      flush(true);
+      return R_OK;
+    }
     NEEDB(32);
     const uint32_t t = peek(32);
     const uint32_t want = ((t & 0xff) << 24) | ((t & 0xff00) << 8) | ((t >> 8) & 0xff00) | (t >> 24);

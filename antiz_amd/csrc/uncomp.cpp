@@ -397,8 +397,9 @@ int main(int argc, char* argv[]) {
       std::cout << "Cannot open file: " << a << std::endl;
       return -1;
     }
-    // ("ATZ\2": a file of the strategy extension, ATZ_STRATEGIES below; same layout)
-    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || (az[3] != 1 && az[3] != 2)) {
+    // ("ATZ\2": a file of the strategy extension, ATZ_STRATEGIES below; "ATZ\3": of the container extension,
+    // ATZ_CONTAINERS; same layout)
+    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 3) {
       std::cout << "Invalid file: ATZ1 header not found" << std::endl;
       return -2;
     }
@@ -450,8 +451,25 @@ int main(int argc, char* argv[]) {
       }
     }
   }
+  // ATZ_CONTAINERS=zip,gzip (any subset; not a reference flag): also recompress the raw deflate bodies of
+  // ZIP entries and gzip members (atz_set_containers)
+  uint32_t containers = 0;
+  if (const char* e = std::getenv("ATZ_CONTAINERS")) {
+    std::stringstream words(e);
+    std::string w;
+    while (std::getline(words, w, ',')) {
+      if (w.empty()) continue;
+      if (w == "zip") containers |= 1u << 0;
+      else if (w == "gzip") containers |= 1u << 1;
+      else {
+        std::cerr << "Error Encountered: " << "ATZ_CONTAINERS: unknown container " << w << std::endl;
+        return done(1);
+      }
+    }
+  }
   if (open_ctx()) return done(255);
   if (strategies && atz_set_strategies(ctx, strategies) != 0) return done(255);
+  if (containers && atz_set_containers(ctx, containers) != 0) return done(255);
   uint8_t* atz = nullptr;
   uint64_t al = 0;
   atz_stats_t st;

@@ -44,7 +44,9 @@ typedef struct {
     uint64_t offset;
     uint64_t comp_len;   /* streamLength */
     uint64_t infl_len;   /* inflatedLength */
-    int32_t  type;       /* offsetType 0..23 */
+    int32_t  type;       /* offsetType 0..23; 24 + hint for a raw deflate body behind a ZIP or gzip header
+                            (only with atz_set_containers; hint 0 none, 1 fast, 2 max): offset is the
+                            body's first byte, comp_len the body's length */
     uint32_t flags;      /* bit0: recorded through a chunk-boundary continuation; bit1: the first block is
                             dynamic and codes matches but none of length 3-5 (a Z_FILTERED-like stream: the
                             multi-GPU split's cost hint, not part of the reference's record); bits 2-5:
@@ -163,6 +165,25 @@ int atz_deflate_batch_ex(atz_ctx_t *ctx, const uint8_t *buf, uint64_t len, const
  * layout; the reference cannot read it), else the file is the ATZ1 of a context without a mask.
  * atz_reconstruct* read both.  The atz_shard_* calls return ATZ_E_ARG on a context with a mask. */
 int atz_set_strategies(atz_ctx_t *ctx, uint32_t mask);
+
+/* Opt-in container anchors (an extension: the reference only knows the 24 zlib headers).  mask bit 0: ZIP
+ * local file headers, bit 1: gzip members; 0, the default, is off and leaves every output as the
+ * reference's.  With a mask, the scan also lists the raw deflate bodies behind such headers that decode to
+ * their end, agree with the container's size fields and meet no reference record (atz_cand_t.type 24 +
+ * hint), and the precompress and sweep calls walk each under the reference's rule over window 15,
+ * memLevels 8, 9, 7..1 and levels 0..9 in the order the container's hint suggests.  A body recorded so
+ * reports clevel = 1<<6 | level, and a file that holds one is written with the magic "ATZ\3" (same layout,
+ * clevel = raw<<6 | strategy<<4 | level; the reference cannot read it), else the file is what a context
+ * without this mask writes.  atz_reconstruct* read all three.  In atz_deflate_batch_ex, bit 28 of a params
+ * word asks for raw output: no zlib header and no Adler-32 trailer.  The atz_shard_* calls return
+ * ATZ_E_ARG on a context with a mask. */
+int atz_set_containers(atz_ctx_t *ctx, uint32_t mask);
+
+/* The anchor kernel's list for a host buffer (parity/debug): *out (atz_free) receives *n entries,
+ * position << 5 | kind (0 ZIP, 1 gzip), ascending.  A ZIP anchor at p: bytes 50 4B 03 04, p + 30 <= len,
+ * method 8, not encrypted.  A gzip anchor: bytes 1F 8B 08, no reserved FLG bit, p + 18 <= len. */
+int atz_container_anchors(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint32_t mask, uint64_t **out,
+                          uint64_t *n);
 
 /* Batch of independent one-shot inflates of the given ranges of a host buffer (parity/debug):
  * status[i] in {0 end, 1 error, 2 need input}, consumed[i] = zlib total_in, produced[i] = total_out. */
