@@ -55,7 +55,8 @@ EXPORTS = ["atz_open", "atz_close", "atz_strerror", "atz_free", "atz_default_opt
            "atz_precompress", "atz_precompress_device", "atz_reconstruct", "atz_deflate", "atz_deflate_batch",
            "atz_inflate_batch", "atz_deflate_bound", "atz_shard_scan", "atz_shard_sweep", "atz_shard_piece",
            "atz_shard_assemble", "atz_reconstruct_device", "atz_deflate_batch_ex", "atz_set_strategies",
-           "atz_set_containers", "atz_container_anchors"]
+           "atz_set_containers", "atz_container_anchors", "atz_set_stitch", "atz_stitch_anchors",
+           "atz_stitch_pieces"]
 
 # zlib's strategy numbers (Z_FIXED, 4, is not supported); a strategy mask has bit k set for strategy k
 STRATEGIES = {"filtered": 1, "huffman": 2, "rle": 3}
@@ -89,6 +90,22 @@ def container_mask(names):
     return mask
 
 
+# what a stitch mask makes the scan put together: bit number of each
+STITCHERS = {"png": 0}
+
+
+def stitch_mask(names):
+    """("png",) or a comma-separated string -> atz_set_stitch mask; ValueError on an unknown word."""
+    if isinstance(names, str):
+        names = [w for w in names.split(",") if w]
+    mask = 0
+    for w in names:
+        if w not in STITCHERS:
+            raise ValueError("unknown stitcher %r (known: %s)" % (w, ", ".join(sorted(STITCHERS))))
+        mask |= 1 << STITCHERS[w]
+    return mask
+
+
 def pack_clevel(strategy, level, raw=False):
     """The clevel byte of an ATZ2 / ATZ3 descriptor (and of atz_sweep's results): raw << 6 | strategy << 4 | level."""
     if not (0 <= strategy <= 3 and 0 <= level <= 9) or (strategy >= 2 and level < 1):
@@ -104,6 +121,19 @@ def unpack_clevel(b):
 def unpack_clevel3(b):
     """-> (raw, strategy, level) of an ATZ3 clevel byte."""
     return bool(b & 0x40), (b >> 4) & 3, b & 15
+
+
+
+def pack_clevel4(strategy, level, raw=False, stitched=False):
+    """The clevel byte of an ATZ4 descriptor: stitched << 7 | raw << 6 | strategy << 4 | level (never both)."""
+    if raw and stitched:
+        raise ValueError("a descriptor is raw or stitched, not both")
+    return (int(bool(stitched)) << 7) | pack_clevel(strategy, level, raw)
+
+
+def unpack_clevel4(b):
+    """-> (stitched, raw, strategy, level) of an ATZ4 clevel byte."""
+    return (bool(b & 0x80),) + unpack_clevel3(b & 0x7f)
 
 _lib = None
 
@@ -148,6 +178,10 @@ def lib():
         L.atz_set_containers.argtypes = [C.c_void_p, C.c_uint32]
         L.atz_container_anchors.argtypes = [C.c_void_p, C.c_char_p, u64, C.c_uint32, C.POINTER(C.POINTER(u64)),
                                             C.POINTER(u64)]
+        L.atz_set_stitch.argtypes = [C.c_void_p, C.c_uint32]
+        L.atz_stitch_anchors.argtypes = L.atz_container_anchors.argtypes
+        L.atz_stitch_pieces.argtypes = [C.c_void_p, u64, C.POINTER(C.POINTER(u64)), C.POINTER(C.POINTER(u64)),
+                                        C.POINTER(u64)]
         L.atz_deflate_bound.restype = u64
         L.atz_deflate_bound.argtypes = [u64, C.c_int, C.c_int]
         L.atz_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, u64, C.c_int, C.c_int, C.POINTER(u8p),
@@ -173,12 +207,14 @@ class Context:
     """One libatz_accel context (one GPU).  Mirrors the reference's programOptions (ATZData.h:7-35)."""
 
     def __init__(self, recomp_tresh=128, sizediff_tresh=128, shortcut_len=512, mismatch_tol=2,
-                 chunksize=524288, brute_window=False, device=-1, strategies=None, containers=None):
+                 chunksize=524288, brute_window=False, device=-1, strategies=None, containers=None, stitch=None):
         """strategies: names of zlib strategies ("filtered", "rle", "huffman") to try on the streams the
         reference walk leaves unrecorded (an extension, off by default; None reads ATZ_STRATEGIES, a
         comma-separated list, as the CLI does).
         containers: "zip", "gzip": also look for the raw deflate bodies of ZIP entries and gzip members (an
-        extension, off by default; None reads ATZ_CONTAINERS, a comma-separated list, as the CLI does)."""
+        extension, off by default; None reads ATZ_CONTAINERS, a comma-separated list, as the CLI does).
+        stitch: "png": also look for zlib streams split over the IDAT chunks of a PNG (an extension, off by
+        default; None reads ATZ_STITCH, a comma-separated list, as the CLI does)."""
         L = lib()
         self.o = Opts(recomp_tresh, sizediff_tresh, shortcut_len, mismatch_tol, chunksize, int(brute_window), device)
         if strategies is None:
@@ -187,12 +223,17 @@ class Context:
         if containers is None:
             containers = os.environ.get("ATZ_CONTAINERS", "")
         cmask = container_mask(containers)
+        if stitch is None:
+            stitch = os.environ.get("ATZ_STITCH", "")
+        smask = stitch_mask(stitch)
         self.h = C.c_void_p()
         _check(L.atz_open(C.byref(self.h), C.byref(self.o)))
         if mask:
             _check(L.atz_set_strategies(self.h, mask))
         if cmask:
             _check(L.atz_set_containers(self.h, cmask))
+        if smask:
+            _check(L.atz_set_stitch(self.h, smask))
 
     def close(self):
         if self.h:
@@ -310,6 +351,27 @@ class Context:
         _check(L.atz_container_anchors(self.h, data, len(data), mask, C.byref(p), C.byref(n)))
         out = [(p[i] >> 5, p[i] & 31) for i in range(n.value)]
         L.atz_free(p)
+        return out
+
+    def stitch_anchors(self, data, mask=1):
+        """The IDAT anchors of `data` (parity/debug): [(position of the chunk type field, 2)], ascending."""
+        L = lib()
+        p = C.POINTER(u64)()
+        n = u64(0)
+        _check(L.atz_stitch_anchors(self.h, data, len(data), mask, C.byref(p), C.byref(n)))
+        out = [(p[i] >> 5, p[i] & 31) for i in range(n.value)]
+        L.atz_free(p)
+        return out
+
+    def stitch_pieces(self, record):
+        """[(file offset, length)] of the pieces of stitched record `record` of the last scan ([]: not stitched)."""
+        L = lib()
+        po, pl = C.POINTER(u64)(), C.POINTER(u64)()
+        k = u64(0)
+        _check(L.atz_stitch_pieces(self.h, record, C.byref(po), C.byref(pl), C.byref(k)))
+        out = [(po[i], pl[i]) for i in range(k.value)]
+        L.atz_free(po)
+        L.atz_free(pl)
         return out
 
     def deflate(self, data, clevel, window, memlevel, strategy=0, raw=False):

@@ -358,6 +358,13 @@ struct Rec {
   uint64_t arena_off = ~0ull;   // scan output kept in the arena (complete), else ~0
   bool noshort = false;         // k_inflate's INF_HINT_NOSHORT (the multi-GPU split's cost estimate)
   uint8_t mhint = 0;            // k_inflate's first-block memLevel (0: none; whole match tables for it)
+  // a stitched record (the stitch extension): its comp_len stream bytes lie contiguous at
+  // this offset of the context's stitch buffer and in the file as pieces [p0, p0 + pk) of st_off / st_len,
+  // 12 framing bytes between two pieces; offset is the first piece's.  ~0: an ordinary record
+  uint64_t stitch = ~0ull;
+  uint32_t p0 = 0, pk = 0;
+  // the file range the record occupies: a stitched one's hull includes the framing between its pieces
+  uint64_t hull() const { return comp_len + (stitch != ~0ull ? 12ull * (pk - 1) : 0); }
 };
 
 struct StreamState {
@@ -671,6 +678,13 @@ struct atz_ctx {
   // opt-in container anchors (atz_set_containers): bit 0 ZIP local file headers, bit 1 gzip members -- raw
   // deflate bodies behind them become records of type 24 + hint, which only raw_pass walks; 0: off
   uint32_t cont_mask = 0;
+  // opt-in stitching (atz_set_stitch): bit 0 PNG IDAT chains -- a zlib stream split over consecutive IDAT
+  // chunks is gathered into d_stitch, decoded and walked there; 0: off.  d_stitch lives until the next scan
+  // (the sweep, the diff lists and the re-inflates read it); st_off / st_len: the pieces of the last scan's
+  // stitched records, file offset and length each (Rec::p0, Rec::pk)
+  uint32_t stitch_mask = 0;
+  DBuf d_stitch;
+  std::vector<uint64_t> st_off, st_len;
   // atz_sweep reports every stream's best ident, c, w, m as the reference computes them; the precompress
   // paths only need what the ATZ1 holds, so they let trials stop once they cannot make their stream
   // recompressible (elig_floor)
@@ -1402,6 +1416,7 @@ static void raw_candidates(const uint8_t* h, uint64_t n, const std::vector<uint6
   for (const uint64_t a : anchors) {
     RawCand r{};
     r.p = a >> 5; r.kind = (int)(a & 31);
+    if (r.kind > 1) continue;   // an IDAT anchor of the same pass (the stitch extension)
     const uint8_t* q = h + r.p;
     if (r.kind == 0) {
       const uint32_t flag = rd2(q + 6);
@@ -1491,6 +1506,168 @@ static int raw_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Opt-in stitching (atz_set_stitch).  A PNG writer cuts one zlib stream into IDAT chunks:
+// every few KiB of it are followed by 12 framing bytes (the chunk's CRC, the next chunk's length, "IDAT"),
+// at which the scan's decode fails.  k_anchors_ordered (kind 2) lists the IDAT type fields in file order;
+// the host links consecutive chunks into chains; k_gather copies each chain's payloads into one contiguous
+// run of the stitch buffer; one k_inflate launch decodes the runs; a stream that ends, crosses a chunk
+// boundary and meets no record made before becomes a record whose original bytes are the stitched copy.
+struct StitchCand {
+  uint64_t at, total;   // the chain's run in the stitch buffer (256-byte aligned), its payload bytes
+  uint32_t p0, pk;      // its pieces in StitchPlan::off / len (the first and the last are not empty)
+  int type;             // header type 0..23 of the run's first two bytes
+};
+struct StitchPlan {
+  std::vector<StitchCand> cands;
+  std::vector<uint64_t> off, len;   // file offset and length of every candidate's payloads
+  uint64_t bytes = 0;               // the stitch buffer's size (without its slack)
+};
+
+// k_anchors_ordered's mask for the context's extensions: the container kinds and, for a stitch mask, kind 2
+static uint32_t ext_anchor_mask(const atz_ctx* c) { return c->cont_mask | ((c->stitch_mask & 1u) ? 4u : 0u); }
+
+static uint64_t be4(const uint8_t* p) { return ((uint64_t)p[0] << 24) | ((uint64_t)p[1] << 16) | ((uint64_t)p[2] << 8) | p[3]; }
+
+// Chains and candidates from the kernel's anchors (position << 5 | 2 among them, ascending) and the host
+// copy.  A cursor walks the file: an anchor below it belongs to no chain; from an anchor a at or past it the
+// chain follows a' = a + L + 12 while a' is an anchor, and the cursor moves to the end of the last chunk's
+// CRC.  So chains are disjoint.  A chain without its leading empty chunks is a candidate if two chunks or
+// more remain and its payloads start with one of the 24 zlib headers (the two bytes may lie in two chunks).
+static void stitch_candidates(const uint8_t* h, const std::vector<uint64_t>& anchors, StitchPlan& P) {
+  P = StitchPlan{};
+  std::vector<uint64_t> A;
+  for (const uint64_t a : anchors)
+    if ((a & 31) == 2) A.push_back(a >> 5);
+  uint64_t cursor = 0;
+  std::vector<std::pair<uint64_t, uint64_t>> ch;   // (payload offset, length)
+  for (size_t i = 0; i < A.size(); i++) {
+    if (A[i] < cursor) continue;
+    ch.clear();
+    uint64_t a = A[i];
+    size_t j = i;
+    for (;;) {
+      const uint64_t L = be4(h + a - 4);
+      ch.push_back({a + 4, L});
+      cursor = a + 8 + L;
+      j = (size_t)(std::lower_bound(A.begin() + j + 1, A.end(), a + L + 12) - A.begin());
+      if (j == A.size() || A[j] != a + L + 12) break;
+      a = A[j];
+    }
+    size_t q = 0;
+    while (q < ch.size() && ch[q].second == 0) q++;
+    if (ch.size() - q < 2) continue;
+    unsigned hb[2] = {0, 0};
+    uint64_t total = 0;
+    for (size_t k = q; k < ch.size(); k++) {
+      for (uint64_t b = 0; b < ch[k].second && total + b < 2; b++) hb[total + b] = h[ch[k].first + b];
+      total += ch[k].second;
+    }
+    const int type = total >= 2 ? header_type_host(hb[0], hb[1]) : -1;
+    if (type < 0) continue;
+    StitchCand cd{P.bytes, total, (uint32_t)P.off.size(), (uint32_t)(ch.size() - q), type};
+    for (size_t k = q; k < ch.size(); k++) { P.off.push_back(ch[k].first); P.len.push_back(ch[k].second); }
+    P.cands.push_back(cd);
+    P.bytes += (total + 255) & ~255ull;
+  }
+}
+
+static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<uint8_t>& meta,
+                           const std::vector<Seg>& segs, uint8_t* dst);
+
+// The stitched records of the file merged into c->recs (the reference's and the raw ones, complete, in file
+// order).  The stitch buffer holds every candidate's run; the chains are disjoint, so the payload bytes
+// gathered never exceed the file's size F, and with each run rounded up to 256 bytes the buffer is at most
+// F + 256 * candidates bytes, plus the 4 KiB of zero slack that d_file has (the kernels read past an end).
+// Outputs go to the scan's arena behind the earlier candidates' (fresh_arena: no job ran before).
+static int stitch_merge(atz_ctx* c, const uint8_t* d_file, uint64_t arena_cap, bool fresh_arena, const StitchPlan& P) {
+  if (P.cands.empty()) return 0;
+  auto tm_ = std::chrono::steady_clock::now();
+  if (int r = c->d_stitch.reserve(P.bytes + 4096)) return r;
+  HIPCHK(hipMemsetAsync(c->d_stitch.as<uint8_t>() + P.bytes, 0, 4096, c->st));
+  std::vector<Seg> segs;
+  std::vector<InfJob> jobs(P.cands.size());
+  for (size_t k = 0; k < P.cands.size(); k++) {
+    const StitchCand& a = P.cands[k];
+    uint64_t at = a.at;
+    for (uint32_t q = a.p0; q < a.p0 + a.pk; q++) {
+      if (P.len[q]) segs.push_back({2, 0, P.off[q], at, P.len[q]});
+      at += P.len[q];
+    }
+    jobs[k] = {a.at, a.total, ARENA_OUT, ARENA_SLOT};
+  }
+  const double other0 = c->stats.k_other_ms, infl0 = c->stats.k_inflate_ms;
+  if (int r = gather_segments(c, d_file, {}, segs, c->d_stitch.as<uint8_t>())) return r;
+  std::vector<InfRes> res;
+  if (int r = run_inflate_jobs(c, c->d_stitch.as<uint8_t>(), nullptr, jobs, res, arena_cap, false, fresh_arena)) return r;
+  if (timing_on())
+    std::fprintf(stderr, "atz: stitch: %zu candidates, %llu bytes in %zu segments, k_gather %.3f ms, k_inflate %.3f ms\n",
+                 P.cands.size(), (unsigned long long)P.bytes, segs.size(), c->stats.k_other_ms - other0,
+                 c->stats.k_inflate_ms - infl0);
+  const std::vector<Rec>& ref = c->recs;
+  std::vector<Rec> acc;
+  for (size_t k = 0; k < P.cands.size(); k++) {
+    const StitchCand& a = P.cands[k];
+    const InfRes& r = res[k];
+    if (r.status != INF_END || r.produced < 1 || r.produced >= (1ull << 31)) continue;
+    if (r.consumed <= P.len[a.p0]) continue;   // ends inside the first chunk: the reference scan's business
+    Rec rec{P.off[a.p0], r.consumed, r.produced, a.type, 0, r.arena_off};
+    rec.noshort = (r.err & INF_HINT_NOSHORT) != 0;
+    rec.mhint = (uint8_t)((r.err >> INF_HINT_MLEV_SHIFT) & 15u);
+    rec.stitch = a.at;
+    rec.p0 = (uint32_t)c->st_off.size();
+    // the pieces the stream touches: the last one ends where the stream does
+    uint64_t sum = 0;
+    for (uint32_t q = a.p0; q < a.p0 + a.pk && sum < r.consumed; q++) {
+      const uint64_t take = std::min<uint64_t>(P.len[q], r.consumed - sum);
+      c->st_off.push_back(P.off[q]); c->st_len.push_back(take);
+      sum += take;
+      rec.pk++;
+    }
+    if (sum != r.consumed) return ATZ_E_INTERNAL;   // (the decoder never reads past the run)
+    // a record made before that meets the hull [offset, offset + hull): the stitched one is dropped
+    const uint64_t lo = rec.offset, hi = rec.offset + rec.hull();
+    const auto it = std::lower_bound(ref.begin(), ref.end(), hi, [](const Rec& x, uint64_t v) { return x.offset < v; });
+    if (it != ref.begin() && (it - 1)->offset + (it - 1)->hull() > lo) {
+      c->st_off.resize(rec.p0); c->st_len.resize(rec.p0);
+      continue;
+    }
+    acc.push_back(rec);
+  }
+  std::vector<Rec> merged;   // (the candidates are in file order and disjoint, as their chains are)
+  merged.reserve(ref.size() + acc.size());
+  size_t i = 0;
+  for (const Rec& e : acc) {
+    while (i < ref.size() && ref[i].offset < e.offset) merged.push_back(ref[i++]);
+    merged.push_back(e);
+  }
+  while (i < ref.size()) merged.push_back(ref[i++]);
+  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
+  c->recs.assign(merged.begin(), merged.end());
+  TMARK("scan: stitched candidates");
+  return 0;
+}
+
+// the last four bytes of record r's stream (its Adler-32 trailer, big-endian) from the host copy h: a
+// stitched record's may straddle its pieces
+static uint32_t rec_trailer(const atz_ctx* c, const Rec& r, const uint8_t* h) {
+  uint32_t t = 0;
+  if (r.stitch == ~0ull) {
+    const uint8_t* e = h + r.offset + r.comp_len;
+    return ((uint32_t)e[-4] << 24) | ((uint32_t)e[-3] << 16) | ((uint32_t)e[-2] << 8) | e[-1];
+  }
+  int got = 0;
+  for (uint32_t q = r.p0 + r.pk; q > r.p0 && got < 4; q--)
+    for (uint64_t b = c->st_len[q - 1]; b > 0 && got < 4; b--, got++) t |= (uint32_t)h[c->st_off[q - 1] + b - 1] << (8 * got);
+  return t;
+}
+
+// where record r's original bytes lie, as an offset from d_file (StreamDev::orig_off, DiffJob::orig_off: the
+// kernels add it to the file base): the stitched copy's 64-bit distance from d_file for a stitched record
+static uint64_t rec_src(const atz_ctx* c, const Rec& r, const uint8_t* d_file) {
+  return r.stitch == ~0ull ? r.offset : (uint64_t)(uintptr_t)c->d_stitch.p + r.stitch - (uint64_t)(uintptr_t)d_file;
+}
+
 // Every record, one piece.  (atz_scan; precompress_dev scans piece by piece while the sweep runs)
 static int scan_impl(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t F) {
   auto t0 = std::chrono::steady_clock::now();
@@ -1499,11 +1676,15 @@ static int scan_impl(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64
   if (int r = scan_plan(c, h, d_file, F, S)) return r;
   std::vector<uint64_t> anchors;
   std::vector<RawCand> rc;
-  if (int r = anchors_dev(c, d_file, F, c->cont_mask, anchors)) return r;
+  StitchPlan sp;
+  if (int r = anchors_dev(c, d_file, F, ext_anchor_mask(c), anchors)) return r;
   raw_candidates(h, F, anchors, rc);
-  c->recs.reserve(S.max_records() + rc.size());
+  stitch_candidates(h, anchors, sp);
+  c->st_off.clear(); c->st_len.clear();
+  c->recs.reserve(S.max_records() + rc.size() + sp.cands.size());
   if (int r = scan_piece(c, h, d_file, S, 0, (uint32_t)S.chunks.size())) return r;
   if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), rc)) return r;
+  if (int r = stitch_merge(c, d_file, S.arena_cap, S.fjobs.empty() && rc.empty(), sp)) return r;
   c->stats.scan_ms = ms_since(t0);
   return 0;
 }
@@ -1519,7 +1700,7 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
   std::vector<uint64_t> loc(r1 - r0);
   for (size_t s = r0; s < r1; s++) {
     const Rec& r = c->recs[s];
-    if (r.offset + r.comp_len > F) return ATZ_E_REF_UB;   // reads past EOF (uninitialised rBuffer)
+    if (r.offset + r.hull() > F) return ATZ_E_REF_UB;   // reads past EOF (uninitialised rBuffer)
     loc[s - r0] = tot;
     tot += (r.infl_len + 255) & ~255ull;
   }
@@ -1528,8 +1709,8 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
   // Streams whose scan decode kept its full output in the arena are copied; the others are
   // inflated again from the file with their exact length (doInflate, main.cpp:461-486) -- the
   // same bytes from the same offset, so both give the same result.
-  std::vector<InfJob> jobs, raw_jobs;
-  std::vector<size_t> job_rec, raw_rec;
+  std::vector<InfJob> jobs, raw_jobs, st_jobs;
+  std::vector<size_t> job_rec, raw_rec, st_rec;
   std::vector<Seg> segs;
   for (size_t s = r0; s < r1; s++) {
     const Rec& r = c->recs[s];
@@ -1539,8 +1720,9 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
     } else {
       InfJob jb;
       jb.in_off = r.offset; jb.in_len = r.comp_len; jb.out_off = loc[s - r0]; jb.out_cap = r.infl_len;
-      (r.type >= 24 ? raw_jobs : jobs).push_back(jb);
-      (r.type >= 24 ? raw_rec : job_rec).push_back(s);
+      if (r.stitch != ~0ull) jb.in_off = r.stitch;   // (its input base is the stitch buffer)
+      (r.stitch != ~0ull ? st_jobs : r.type >= 24 ? raw_jobs : jobs).push_back(jb);
+      (r.stitch != ~0ull ? st_rec : r.type >= 24 ? raw_rec : job_rec).push_back(s);
     }
   }
   if (!segs.empty()) {
@@ -1563,6 +1745,13 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
     job_rec.insert(job_rec.end(), raw_rec.begin(), raw_rec.end());
     res.insert(res.end(), rres.begin(), rres.end());
   }
+  if (!st_jobs.empty()) {   // stitched records (the stitch extension): from their contiguous copies
+    std::vector<InfRes> sres;
+    if (int r = run_inflate_jobs(c, c->d_stitch.as<uint8_t>(), slab.as<uint8_t>(), st_jobs, sres)) return r;
+    jobs.insert(jobs.end(), st_jobs.begin(), st_jobs.end());
+    job_rec.insert(job_rec.end(), st_rec.begin(), st_rec.end());
+    res.insert(res.end(), sres.begin(), sres.end());
+  }
   if (timing_on()) {
     uint64_t mx = 0, tot = 0;
     for (const InfJob& jb : jobs) { mx = std::max(mx, jb.in_len); tot += jb.in_len; }
@@ -1579,11 +1768,8 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
   for (size_t s = r0; s < r1; s++) {
     // Adler-32 of the inflated bytes = the verified trailer (atz_sweep: saved by atz_scan, whose
     // host buffer the caller need not keep alive)
-    const uint64_t e = c->recs[s].offset + c->recs[s].comp_len;
     if (c->recs[s].type >= 24) { c->adler[s] = 0; continue; }   // a raw body has no trailer (TM_RAW trials write none)
-    c->adler[s] = c->hfile ? ((uint32_t)c->hfile[e - 4] << 24) | ((uint32_t)c->hfile[e - 3] << 16) |
-                                 ((uint32_t)c->hfile[e - 2] << 8) | c->hfile[e - 1]
-                           : c->scan_trailer[s];
+    c->adler[s] = c->hfile ? rec_trailer(c, c->recs[s], c->hfile) : c->scan_trailer[s];
   }
   HIPCHK(hipStreamSynchronize(c->st));
   kcollect(c);
@@ -2888,7 +3074,7 @@ struct Round : TrialBatch {
         st.first_diff = -1;
         st.rawdiff.clear(); st.diffval.clear();
         pend[a].live = step.diff;   // an earlier improvement's diffs are superseded
-        if (step.diff) pend[a].d = DiffJob{t.out_off, r.out_len, x->recs[s].offset, C, 0, C - r.ident};
+        if (step.diff) pend[a].d = DiffJob{t.out_off, r.out_len, rec_src(x, x->recs[s], d_file), C, 0, C - r.ident};
       }
       st.idx++;
       if (step.stop) st.idx = (uint32_t)st.list->size();   // testParamRange/tryParams return
@@ -3215,7 +3401,7 @@ static int sweep_publish(atz_ctx* c, SweepRun& R, size_t r0, size_t r1) {
   if (r1 > R.sd.size()) return ATZ_E_INTERNAL;
   for (size_t s = r0; s < r1; s++) {
     StreamDev& d = R.sd[s];
-    d.orig_off = c->recs[s].offset; d.infl_off = c->infl_off[s];
+    d.orig_off = rec_src(c, c->recs[s], R.d_file); d.infl_off = c->infl_off[s];
     d.comp_len = c->recs[s].comp_len; d.infl_len = c->recs[s].infl_len;
     (*R.ss)[s].list = &trial_list(c->recs[s].type, false);
   }
@@ -3495,7 +3681,7 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
           e.rawdiff.clear(); e.diffval.clear();
           e.done = step.stop;
           if (step.diff) {
-            dj.push_back(DiffJob{t.out_off, r.out_len, c->recs[s].offset, C, 0, C - r.ident});
+            dj.push_back(DiffJob{t.out_off, r.out_len, rec_src(c, c->recs[s], d_file), C, 0, C - r.ident});
             djs.push_back(s);
           }
         }
@@ -3581,7 +3767,8 @@ static void atz_descriptors(atz_ctx* c, const std::vector<StreamState>& ss, std:
     const Rec& r = c->recs[s];
     const size_t m0 = meta.size();   // the stream descriptor goes straight into meta
     put8(meta, r.offset); put8(meta, r.comp_len); put8(meta, r.infl_len);
-    meta.push_back(st.c); meta.push_back(st.w); meta.push_back(st.m);
+    // (version 4: bit 7 of the clevel byte marks a stitched descriptor, whose piece list follows its payload)
+    meta.push_back((uint8_t)(st.c | (r.stitch != ~0ull ? 0x80 : 0))); meta.push_back(st.w); meta.push_back(st.m);
     uint64_t nd = st.rawdiff.size();
     put8(meta, nd);
     if (nd) {
@@ -3593,6 +3780,14 @@ static void atz_descriptors(atz_ctx* c, const std::vector<StreamState>& ss, std:
     out += meta.size() - m0;
     segs.push_back({1, 0, c->infl_off[s], out, r.infl_len});   // absolute address (INFL_BASE)
     out += r.infl_len;
+    if (r.stitch != ~0ull) {   // u32 k, k x u32 piece lengths (piece i starts at offset + sum_{j<i} (len_j + 12))
+      const size_t m1 = meta.size();
+      auto put4 = [&](uint32_t v) { uint8_t b[4]; std::memcpy(b, &v, 4); meta.insert(meta.end(), b, b + 4); };
+      put4(r.pk);
+      for (uint32_t q = r.p0; q < r.p0 + r.pk; q++) put4((uint32_t)c->st_len[q]);
+      segs.push_back({0, 0, m1, out, meta.size() - m1});
+      out += meta.size() - m1;
+    }
   }
 }
 
@@ -3647,19 +3842,28 @@ static int write_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::
   std::vector<Seg> segs;
   const size_t n = c->recs.size();
   uint64_t nrec = 0;
-  uint8_t version = 1;   // ATZ1 unless a recorded stream carries a strategy (2) or is raw (3)
+  uint8_t version = 1;   // ATZ1 unless a recorded stream carries a strategy (2), is raw (3) or is stitched (4)
+  size_t npieces = 0;
   for (size_t s = 0; s < n; s++) {
     nrec += ss[s].recomp;
     if (ss[s].recomp && (ss[s].c >> 4)) version = std::max<uint8_t>(version, (ss[s].c & 0x40) ? 3 : 2);
+    if (ss[s].recomp && c->recs[s].stitch != ~0ull) version = 4;
+    npieces += c->recs[s].stitch != ~0ull ? c->recs[s].pk : 1;
   }
   atz_header(meta, F, nrec, version);
   segs.push_back({0, 0, 0, 0, meta.size()});
   uint64_t out = meta.size();
   meta.reserve(meta.size() + nrec * 43 + 64);
   atz_descriptors(c, ss, meta, segs, out);
-  std::vector<std::pair<uint64_t, uint64_t>> rec(n);
-  std::vector<uint8_t> rc(n);
-  for (size_t s = 0; s < n; s++) { rec[s] = {c->recs[s].offset, c->recs[s].comp_len}; rc[s] = ss[s].recomp; }
+  // (a stitched record occupies one range per piece: the framing between them is residue)
+  std::vector<std::pair<uint64_t, uint64_t>> rec;
+  std::vector<uint8_t> rc;
+  rec.reserve(npieces); rc.reserve(npieces);
+  for (size_t s = 0; s < n; s++) {
+    const Rec& r = c->recs[s];
+    if (r.stitch == ~0ull) { rec.push_back({r.offset, r.comp_len}); rc.push_back(ss[s].recomp); continue; }
+    for (uint32_t q = r.p0; q < r.p0 + r.pk; q++) { rec.push_back({c->st_off[q], c->st_len[q]}); rc.push_back(ss[s].recomp); }
+  }
   if (int r = atz_residue(rec, rc.data(), F, segs, out)) return r;
   std::memcpy(meta.data() + 4, &out, 8);   // back-patched length (main.cpp:797-800)
   if (int r = c->d_atz.reserve(out + 4096)) return r;
@@ -3691,13 +3895,17 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   ScanState& S = *c->scan_keep;
   if (int r = scan_plan(c, h, d_file, F, S)) return r;
   // the container extension's candidates (none without a mask): the sweep's tables have room for them
+  // (and the stitch extension's, likewise)
   std::vector<RawCand> raw_cands;
-  if (c->cont_mask) {
+  StitchPlan stitch_plan;
+  c->st_off.clear(); c->st_len.clear();
+  if (ext_anchor_mask(c)) {
     std::vector<uint64_t> anchors;
-    if (int r = anchors_dev(c, d_file, F, c->cont_mask, anchors)) return r;
+    if (int r = anchors_dev(c, d_file, F, ext_anchor_mask(c), anchors)) return r;
     raw_candidates(h, F, anchors, raw_cands);
+    stitch_candidates(h, anchors, stitch_plan);
   }
-  const size_t n_max = S.max_records() + raw_cands.size();
+  const size_t n_max = S.max_records() + raw_cands.size() + stitch_plan.cands.size();
   c->recs.reserve(n_max);
   std::vector<StreamState>& ss = c->ss_keep;
   SweepRun R;
@@ -3723,8 +3931,8 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   });
   struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join_begin{t_begin};
   double scan_busy = ms_since(t0);
-  // (with a container mask the raw records need the reference's final ones: scan, merge, then sweep)
-  const bool spec = P == 1 && spec_cont_on() && !c->cont_mask;
+  // (with a container or stitch mask the added records need the reference's final ones: scan, merge, then sweep)
+  const bool spec = P == 1 && spec_cont_on() && !ext_anchor_mask(c);
   if (spec) {
     // The first continuations of pending streams (each a decode of the stream from its header through
     // the chunk boundary) are latency-bound: one small launch, 15-30 ms.  The records do not wait for
@@ -3790,6 +3998,7 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
     const size_t r0 = c->recs.size();
     if (int r = scan_piece(c, h, d_file, S, ja, jb)) return r;
     if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), raw_cands)) return r;
+    if (int r = stitch_merge(c, d_file, S.arena_cap, S.fjobs.empty() && raw_cands.empty(), stitch_plan)) return r;
     if (p == 0) {
       t_begin.join();
       if (rc_begin) return rc_begin;
@@ -3930,15 +4139,34 @@ static int deflate_many(atz_ctx* c, const std::vector<std::pair<const uint8_t*, 
 // Adler-32 on the device, one deflate per stream (doDeflate, main.cpp:976-1003), diff bytes patched
 // (main.cpp:916-926) and the original assembled in c->d_rec by k_gather: residue gaps, the first
 // comp_len bytes of each deflate output (zero-extended, as the reference's buffer is), the tail.
-struct AtzDesc { uint64_t off, cl, il, nd, fd, dpos, ipos; uint8_t c, w, m; };
+// (k, ppos: a stitched descriptor's piece count and the position of its k u32 piece lengths; k = 0: not stitched)
+struct AtzDesc {
+  uint64_t off, cl, il, nd, fd, dpos, ipos; uint8_t c, w, m;
+  uint64_t k = 0, ppos = 0;
+  uint64_t hull() const { return cl + (k ? 12 * (k - 1) : 0); }
+};
+static uint32_t rd4le(const uint8_t* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
+// stream range [a, b) of a stitched descriptor, cut at its pieces: fn(stream position, file position, length)
+template <class F>
+static void stitched_ranges(const uint8_t* atz, const AtzDesc& x, uint64_t a, uint64_t b, F fn) {
+  uint64_t sp = 0, fp = x.off;   // the piece's first byte in the stream and in the file
+  for (uint64_t i = 0; i < x.k && sp < b; i++) {
+    const uint64_t len = rd4le(atz + x.ppos + 4 * i);
+    const uint64_t lo = std::max(a, sp), hi = std::min(b, sp + len);
+    if (lo < hi) fn(lo, fp + (lo - sp), hi - lo);
+    sp += len; fp += len + 12;
+  }
+}
 
 // ATZ1 parse with the reference's checks (main.cpp:1011-1063); every size field is bounded by the
 // bytes actually left before anything is sized from it (subtraction-only checks: no sum can wrap)
 static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, uint64_t& origlen, uint64_t& residue) {
   // version 2: the strategy extension's files (same layout; clevel = strategy << 4 | level)
   // version 3: the container extension's (clevel = raw << 6 | strategy << 4 | level)
-  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 3) return ATZ_E_FORMAT;   // main.cpp:1018-1021
-  const bool v2 = atz[3] == 2, v3 = atz[3] == 3;
+  // version 4: the stitch extension's (clevel = stitched << 7 | raw << 6 | strategy << 4 | level, never both
+  // of bits 6 and 7; a stitched descriptor's piece list follows its payload: u32 k, k x u32 lengths)
+  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 4) return ATZ_E_FORMAT;   // main.cpp:1018-1021
+  const bool v2 = atz[3] == 2, v4 = atz[3] == 4, v3 = atz[3] == 3 || v4;
   if (rd8(atz + 4) != n) return ATZ_E_FORMAT;                              // main.cpp:1022-1025
   origlen = rd8(atz + 12);
   const uint64_t nstrms = rd8(atz + 20);
@@ -3971,7 +4199,20 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
     }
     if (v3) {
       const uint32_t sg = (x.c >> 4) & 3u;
-      if ((x.c & 0x80) || (x.c & 15) > 9 || sg > 3 || (sg >= 2 && (x.c & 15) < 1)) return ATZ_E_REF_ABORT;
+      const bool stitched = v4 && (x.c & 0x80);
+      if (((x.c & 0x80) && !v4) || (stitched && (x.c & 0x40)) || (x.c & 15) > 9 || sg > 3 || (sg >= 2 && (x.c & 15) < 1))
+        return ATZ_E_REF_ABORT;
+      if (stitched) {   // k >= 2 pieces, the first and the last not empty, their lengths summing to comp_len
+        if (n - lastos < 4) return ATZ_E_FORMAT;
+        x.k = rd4le(atz + lastos);
+        if (x.k < 2 || x.k > (n - lastos - 4) / 4) return ATZ_E_FORMAT;
+        x.ppos = lastos + 4;
+        lastos = x.ppos + 4 * x.k;
+        uint64_t sum = 0;
+        for (uint64_t i = 0; i < x.k; i++) sum += rd4le(atz + x.ppos + 4 * i);
+        if (sum != x.cl || rd4le(atz + x.ppos) < 1 || rd4le(atz + x.ppos + 4 * (x.k - 1)) < 1) return ATZ_E_FORMAT;
+        x.c &= 0x7f;
+      }
     } else if (v2) {   // Z_HUFFMAN_ONLY and Z_RLE have no level 0
       if ((x.c & 15) > 9 || (x.c >> 4) > 3 || ((x.c >> 4) >= 2 && (x.c & 15) < 1)) return ATZ_E_REF_ABORT;
     } else if (x.c > 9) return ATZ_E_REF_ABORT;
@@ -3982,7 +4223,8 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
   uint64_t end = 0;
   for (uint64_t j = 0; j < nstrms; j++) {
     if (d[j].off < end || d[j].off > origlen || d[j].cl > origlen - d[j].off) return ATZ_E_FORMAT;
-    end = d[j].off + d[j].cl;
+    if (d[j].k && (d[j].k - 1 > (origlen - d[j].off - d[j].cl) / 12)) return ATZ_E_FORMAT;   // the hull inside the original
+    end = d[j].off + d[j].hull();
   }
   residue = lastos;
   // the residue must hold every gap and the tail
@@ -4003,16 +4245,26 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
   std::vector<uint8_t> meta(8, 0);
   uint64_t gapsum = 0, lo = 0, ll = 0, out = 0;
   // residue gaps and the tail are plain copies; the streams' segments come from their batches
+  // (a stitched stream's pieces each take their place: the 12 framing bytes between two are a gap)
   std::vector<uint64_t> rec_off(ns);
-  for (size_t j = 0; j < ns; j++) {
-    if (lo + ll != d[j].off) {
-      const uint64_t g = d[j].off - (lo + ll);   // > 0: offsets checked ascending
+  auto place = [&](uint64_t off, uint64_t len) {
+    if (lo + ll != off) {
+      const uint64_t g = off - (lo + ll);   // > 0: offsets checked ascending
       segs.push_back({2, 0, residue + gapsum, out, g});
       gapsum += g; out += g;
     }
-    rec_off[j] = out;
-    out += d[j].cl;
-    lo = d[j].off; ll = d[j].cl;
+    out += len;
+    lo = off; ll = len;
+  };
+  for (size_t j = 0; j < ns; j++) {
+    if (!d[j].k) { place(d[j].off, d[j].cl); rec_off[j] = out - d[j].cl; continue; }
+    rec_off[j] = d[j].off;   // (out == off at a stream's first byte: gaps and streams fill the original in order)
+    uint64_t fp = d[j].off;
+    for (uint64_t i = 0; i < d[j].k; i++) {
+      const uint64_t len = rd4le(h + d[j].ppos + 4 * i);
+      place(fp, len);
+      fp += len + 12;
+    }
   }
   if (lo + ll < origlen) { segs.push_back({2, 0, residue + gapsum, out, origlen - (lo + ll)}); out += origlen - (lo + ll); }
   if (out != origlen) return ATZ_E_FORMAT;
@@ -4059,11 +4311,20 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
         const uint64_t L = ol[j - s0], cl = d[j].cl;
         if (L > cl + 65535) return ATZ_E_REF_ABORT;   // deflate() != Z_STREAM_END in a cl+65535 buffer
         const uint64_t k = L < cl ? L : cl;
-        if (k) sg.push_back({1, 0, oa[j - s0], rec_off[j], k});
-        if (cl > k) sg.push_back({3, 0, 0, rec_off[j] + k, cl - k});   // zero-extended buffer
+        if (d[j].k) {
+          // a stitched stream: its bytes go straight to their pieces' file positions -- the output ranges, the
+          // zero extension and (below) each diff position are mapped through the piece prefix sums
+          stitched_ranges(h, d[j], 0, k, [&](uint64_t sp, uint64_t fp, uint64_t len) { sg.push_back({1, 0, oa[j - s0] + sp, fp, len}); });
+          stitched_ranges(h, d[j], k, cl, [&](uint64_t, uint64_t fp, uint64_t len) { sg.push_back({3, 0, 0, fp, len}); });
+        } else {
+          if (k) sg.push_back({1, 0, oa[j - s0], rec_off[j], k});
+          if (cl > k) sg.push_back({3, 0, 0, rec_off[j] + k, cl - k});   // zero-extended buffer
+        }
         // diff bytes: positions first_diff + prefix sums of the deltas; only those < cl reach the output
         if (d[j].nd) {
           const size_t p0 = pat.size();
+          std::vector<uint64_t> pre;   // a stitched stream's pieces: the stream position each starts at
+          for (uint64_t i = 0, sp = 0; i < d[j].k; i++) { pre.push_back(sp); sp += rd4le(h + d[j].ppos + 4 * i); }
           uint64_t sum = 0;
           bool increasing = true;
           for (uint64_t i = 0; i < d[j].nd; i++) {
@@ -4071,8 +4332,11 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
             const uint64_t at = d[j].fd + delta + sum;
             sum += delta;
             if (at < cl) {
-              if (pat.size() > p0 && rb + rec_off[j] + at <= pat.back()) increasing = false;
-              pat.push_back(rb + rec_off[j] + at);
+              uint64_t to = rec_off[j] + at;
+              if (d[j].k)   // behind i pieces' framing: i = the last piece that starts at or before `at`
+                to += 12 * (uint64_t)(std::upper_bound(pre.begin(), pre.end(), at) - pre.begin() - 1);
+              if (pat.size() > p0 && rb + to <= pat.back()) increasing = false;
+              pat.push_back(rb + to);
               pval.push_back(h[d[j].dpos + 8 * d[j].nd + i]);
             }
           }
@@ -4389,9 +4653,8 @@ int atz_scan(atz_ctx_t* c, const uint8_t* file, uint64_t len, atz_cand_t** out, 
     c->scan_trailer.assign(c->recs.size(), 0);
     for (size_t s = 0; s < c->recs.size(); s++) {
       const Rec& r = c->recs[s];
-      if (r.comp_len < 4 || r.offset + r.comp_len > len) continue;   // atz_sweep reports ATZ_E_REF_UB
-      const uint8_t* e = file + r.offset + r.comp_len;
-      c->scan_trailer[s] = ((uint32_t)e[-4] << 24) | ((uint32_t)e[-3] << 16) | ((uint32_t)e[-2] << 8) | e[-1];
+      if (r.comp_len < 4 || r.offset + r.hull() > len) continue;   // atz_sweep reports ATZ_E_REF_UB
+      c->scan_trailer[s] = rec_trailer(c, r, file);
     }
     *n = c->recs.size();
     *out = (atz_cand_t*)std::malloc((c->recs.size() + 1) * sizeof(atz_cand_t));
@@ -4399,7 +4662,8 @@ int atz_scan(atz_ctx_t* c, const uint8_t* file, uint64_t len, atz_cand_t** out, 
     for (size_t s = 0; s < c->recs.size(); s++) {
       (*out)[s].offset = c->recs[s].offset; (*out)[s].comp_len = c->recs[s].comp_len;
       (*out)[s].infl_len = c->recs[s].infl_len; (*out)[s].type = c->recs[s].type;
-      (*out)[s].flags = c->recs[s].flags | (c->recs[s].noshort ? 2u : 0u) | ((uint32_t)c->recs[s].mhint << 2);
+      (*out)[s].flags = c->recs[s].flags | (c->recs[s].noshort ? 2u : 0u) | ((uint32_t)c->recs[s].mhint << 2) |
+                        (c->recs[s].stitch != ~0ull ? 64u : 0u);
     }
     c->scan_valid = true;
     return ATZ_OK;
@@ -4663,6 +4927,43 @@ int atz_container_anchors(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint3
   });
 }
 
+int atz_set_stitch(atz_ctx_t* c, uint32_t mask) {
+  if (!c || (mask & ~1u)) return ATZ_E_ARG;   // bit 0: PNG IDAT chains
+  c->stitch_mask = mask;
+  c->scan_valid = false;
+  return ATZ_OK;
+}
+
+int atz_stitch_anchors(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint32_t mask, uint64_t** out, uint64_t* n) {
+  return guarded([&]() -> int {
+    (void)hipGetLastError();
+    if (!c || (!file && len) || !out || !n || (mask & ~1u)) return ATZ_E_ARG;
+    c->scan_valid = false; c->shard.stage = 0;   // d_file is replaced
+    if (int r = upload(c, c->d_file, file, len)) return r;
+    std::vector<uint64_t> a;
+    if (int r = anchors_dev(c, c->d_file.as<uint8_t>(), len, (mask & 1u) ? 4u : 0u, a)) return r;
+    *out = (uint64_t*)std::malloc((a.size() + 1) * 8);
+    if (!*out) return ATZ_E_NOMEM;
+    if (!a.empty()) std::memcpy(*out, a.data(), a.size() * 8);
+    *n = a.size();
+    return ATZ_OK;
+  });
+}
+
+int atz_stitch_pieces(atz_ctx_t* c, uint64_t record, uint64_t** offs, uint64_t** lens, uint64_t* k) {
+  return guarded([&]() -> int {
+    if (!c || !offs || !lens || !k || !c->scan_valid || record >= c->recs.size()) return ATZ_E_ARG;
+    const Rec& r = c->recs[record];
+    const uint64_t n = r.stitch != ~0ull ? r.pk : 0;
+    *offs = (uint64_t*)std::malloc((n + 1) * 8);
+    *lens = (uint64_t*)std::malloc((n + 1) * 8);
+    if (!*offs || !*lens) { std::free(*offs); std::free(*lens); return ATZ_E_NOMEM; }
+    for (uint64_t q = 0; q < n; q++) { (*offs)[q] = c->st_off[r.p0 + q]; (*lens)[q] = c->st_len[r.p0 + q]; }
+    *k = n;
+    return ATZ_OK;
+  });
+}
+
 int atz_inflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
                       uint64_t n, uint32_t* status, uint64_t* consumed, uint64_t* produced) {
   return guarded([&]() -> int {
@@ -4689,7 +4990,7 @@ int atz_shard_scan(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, u
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !blob || !blob_len || world < 1 || rank < 0 || rank >= world) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
+    if (c->strat_mask || c->cont_mask || c->stitch_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
     dev_mark_call();   // (the peak runs on through atz_shard_sweep, whose stats report it)
     std::vector<uint64_t> b;
     if (int r = shard_scan_impl(c, d_file, h_file, len, rank, world, b)) { c->shard.stage = 0; return r; }
@@ -4707,7 +5008,7 @@ int atz_shard_sweep(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, 
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !piece_len || !recomp_flags || !n_flags || !n_recomp) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask) return ATZ_E_ARG;
+    if (c->strat_mask || c->cont_mask || c->stitch_mask) return ATZ_E_ARG;
     std::vector<uint8_t> f;
     if (int r = shard_sweep_impl(c, d_file, h_file, len, blobs, blob_lens, world, f, n_recomp)) {
       c->shard.stage = 0;

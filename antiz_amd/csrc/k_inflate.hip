@@ -181,6 +181,9 @@ __global__ __launch_bounds__(256) void k_headers_ordered(const uint8_t* __restri
 // Container anchors (the opt-in container extension): the fixed part of a ZIP local file
 // header (kind 0, mask bit 0) or of a gzip member header (kind 1, mask bit 1) starts at p.  Every byte
 // read lies inside the file: the length test comes first.  -1: no anchor.
+// Kind 2 (mask bit 2, internal: the stitch extension; atz_container_anchors never passes it):
+// p is the 'I' of a PNG chunk type field "IDAT" whose big-endian length L at p - 4 is below 2^31 and whose
+// payload and CRC lie inside the file, p + 8 + L <= n.
 __device__ inline int anchor_kind(const uint8_t* __restrict__ f, uint64_t p, uint64_t n, uint32_t mask) {
   const uint32_t b0 = f[p];
   if (b0 == 0x50 && (mask & 1u)) {
@@ -195,6 +198,14 @@ __device__ inline int anchor_kind(const uint8_t* __restrict__ f, uint64_t p, uin
     if (f[p + 1] != 0x8b || f[p + 2] != 0x08) return -1;
     if (f[p + 3] & 0xe0) return -1;                  // reserved FLG bits
     return 1;
+  }
+  if (b0 == 0x49 && (mask & 4u)) {
+    if (p < 4 || p + 8 > n) return -1;
+    if (f[p + 1] != 0x44 || f[p + 2] != 0x41 || f[p + 3] != 0x54) return -1;
+    const uint64_t L = ((uint64_t)f[p - 4] << 24) | ((uint64_t)f[p - 3] << 16) | ((uint64_t)f[p - 2] << 8) | f[p - 1];
+    if (L >> 31) return -1;
+    if (L > n - p - 8) return -1;                    // payload + CRC end past the file
+    return 2;
   }
   return -1;
 }
@@ -229,7 +240,7 @@ __global__ __launch_bounds__(256) void k_anchors_ordered(const uint8_t* __restri
       for (int k = 0; k < 16; k++) {
         const uint32_t x = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w;
         const uint32_t b = (x >> (8 * (k & 3))) & 0xff;
-        if (((b == 0x50 && (mask & 1u)) || (b == 0x1f && (mask & 2u))) && p + k < s1 &&
+        if (((b == 0x50 && (mask & 1u)) || (b == 0x1f && (mask & 2u)) || (b == 0x49 && (mask & 4u))) && p + k < s1 &&
             anchor_kind(f, p + k, n, mask) >= 0)
           hits |= 1u << k;
       }

@@ -398,8 +398,9 @@ int main(int argc, char* argv[]) {
       return -1;
     }
     // ("ATZ\2": a file of the strategy extension, ATZ_STRATEGIES below; "ATZ\3": of the container extension,
-    // ATZ_CONTAINERS; same layout)
-    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 3) {
+    // ATZ_CONTAINERS; same layout; "ATZ\4": of the stitch extension, ATZ_STITCH, whose stitched descriptors carry a
+    // piece list)
+    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 4) {
       std::cout << "Invalid file: ATZ1 header not found" << std::endl;
       return -2;
     }
@@ -467,9 +468,25 @@ int main(int argc, char* argv[]) {
       }
     }
   }
+  // ATZ_STITCH=png (not a reference flag): also recompress zlib streams split over the IDAT chunks of a PNG
+  // (atz_set_stitch)
+  uint32_t stitch = 0;
+  if (const char* e = std::getenv("ATZ_STITCH")) {
+    std::stringstream words(e);
+    std::string w;
+    while (std::getline(words, w, ',')) {
+      if (w.empty()) continue;
+      if (w == "png") stitch |= 1u << 0;
+      else {
+        std::cerr << "Error Encountered: " << "ATZ_STITCH: unknown stitcher " << w << std::endl;
+        return done(1);
+      }
+    }
+  }
   if (open_ctx()) return done(255);
   if (strategies && atz_set_strategies(ctx, strategies) != 0) return done(255);
   if (containers && atz_set_containers(ctx, containers) != 0) return done(255);
+  if (stitch && atz_set_stitch(ctx, stitch) != 0) return done(255);
   uint8_t* atz = nullptr;
   uint64_t al = 0;
   atz_stats_t st;

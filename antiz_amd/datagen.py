@@ -121,7 +121,8 @@ def _jar_entry(rng, k):
 
 
 def _c3_piece(args):
-    seed, target = args
+    seed, target = args[:2]
+    idat = args[2] if len(args) > 2 else 0   # gen_c3_chunked: the PNG-like streams cut into IDAT chunks
     rng = np.random.default_rng(seed)
     out, size, k = [], 0, 0
     while size < target:
@@ -132,7 +133,11 @@ def _c3_piece(args):
                     b"\nendstream\nendobj\n"
         elif u < 0.8:
             s = _png_like(rng, int(rng.integers(8192, 65537)))
-            piece = struct.pack(">I", len(s)) + b"IDAT" + s + b"\0\0\0\0"
+            if idat:   # as a PNG writer does: every `idat` bytes a chunk of its own, real lengths and CRCs
+                piece = b"".join(struct.pack(">I", len(p)) + b"IDAT" + p + struct.pack(">I", zlib.crc32(b"IDAT" + p))
+                                 for p in (s[at:at + idat] for at in range(0, len(s), idat)))
+            else:
+                piece = struct.pack(">I", len(s)) + b"IDAT" + s + b"\0\0\0\0"
         else:
             piece = _jar_entry(rng, k)
         out.append(piece)
@@ -167,6 +172,15 @@ def gen_c3(seed=3, total=100 * 1000 * 1000, workers=None):
     workers = workers or min(16, os.cpu_count() or 1)
     pieces = 64
     return _parallel(_c3_piece, [(seed * 1000003 + i, total // pieces) for i in range(pieces)], workers)
+
+
+def gen_c3_chunked(idat=8192, seed=3, total=100 * 1000 * 1000, workers=None):
+    """C3 with every PNG-like stream cut into IDAT chunks of `idat` bytes (libpng's default is 8192), each with
+    its real length and CRC-32: one zlib stream interrupted by 12 framing bytes every `idat` bytes, which only
+    the stitch extension records.  The streams themselves are C3's."""
+    workers = workers or min(16, os.cpu_count() or 1)
+    pieces = 64
+    return _parallel(_c3_piece, [(seed * 1000003 + i, total // pieces, int(idat)) for i in range(pieces)], workers)
 
 
 def gen_c4(seed=4, n_streams=100000, wrange=None, workers=None):
@@ -222,7 +236,7 @@ def gen_near(seed=71, n_streams=600):
 
 
 CONFIGS = {"c1": gen_c1, "c2": gen_c2, "c3": gen_c3, "c4": gen_c4, "c5": gen_c5, "c4c3": gen_c4c3,
-           "near": gen_near}
+           "near": gen_near, "c3_chunked": gen_c3_chunked}
 
 
 def cached(name, cache_dir, **kw):

@@ -17,6 +17,9 @@
  *   atz_deflate     one deflateInit2/deflate(Z_FINISH)/deflateEnd              main.cpp:976-1003
  *   atz_shard_*     the precompress of one file split over several GPUs (new: the reference is
  *                   single-threaded)
+ * Three opt-in extensions, each off by default and leaving every output as the reference's while off:
+ *   atz_set_strategies  zlib strategy trials ("ATZ\2"), atz_set_containers  raw deflate in ZIP / gzip ("ATZ\3"),
+ *   atz_set_stitch      zlib streams split over PNG IDAT chunks ("ATZ\4")
  */
 #ifndef ATZ_ACCEL_H
 #define ATZ_ACCEL_H
@@ -51,7 +54,10 @@ typedef struct {
                             dynamic and codes matches but none of length 3-5 (a Z_FILTERED-like stream: the
                             multi-GPU split's cost hint, not part of the reference's record); bits 2-5:
                             the memLevel (1-9) whose lit_bufsize - 1 symbols the first block holds when
-                            more blocks follow, else 0 (a sweep hint, likewise not the reference's) */
+                            more blocks follow, else 0 (a sweep hint, likewise not the reference's); bit 6: a
+                            stitched record (only with atz_set_stitch): a zlib stream split over k >= 2 PNG IDAT
+                            chunks -- offset is its first payload byte, comp_len its length in stream bytes, and
+                            it occupies [offset, offset + comp_len + 12 (k - 1)) of the file (atz_stitch_pieces) */
 } atz_cand_t;
 
 /* ATZdata::streamOffset after Phase 3. */
@@ -184,6 +190,31 @@ int atz_set_containers(atz_ctx_t *ctx, uint32_t mask);
  * method 8, not encrypted.  A gzip anchor: bytes 1F 8B 08, no reserved FLG bit, p + 18 <= len. */
 int atz_container_anchors(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint32_t mask, uint64_t **out,
                           uint64_t *n);
+
+/* Opt-in stitching (an extension: the reference only decodes contiguous streams).  mask bit 0: PNG IDAT
+ * chains; 0, the default, is off and leaves every output as what a context without this mask writes.  A PNG
+ * writer cuts its one zlib stream into IDAT chunks, so 12 framing bytes (CRC, length, "IDAT") interrupt it
+ * every few KiB and the scan's decode fails there.  With the mask, the scan also links consecutive IDAT
+ * chunks into chains, decodes each chain's concatenated payloads, and lists a stream that ends (Adler-32
+ * checked), crosses a chunk boundary and whose hull meets no other record: atz_cand_t.type is its header's
+ * 0..23, flags bit 6 is set.  The precompress and sweep calls walk it as any stream of its type (the
+ * reference walk, then the strategy walk under atz_set_strategies).  A file that records one is written with
+ * the magic "ATZ\4": clevel = stitched<<7 | raw<<6 | strategy<<4 | level (never both of bits 6 and 7), and a
+ * stitched descriptor carries, after its inflated payload, u32 k and k x u32 piece lengths (little-endian;
+ * piece i starts at offset + sum_{j<i} (len_j + 12); diff positions are stream positions; the framing bytes
+ * are residue).  Else the file is what a context without this mask writes.  atz_reconstruct* read all four.
+ * atz_sweep's clevel never carries bit 7.  The atz_shard_* calls return ATZ_E_ARG on a context with a mask. */
+int atz_set_stitch(atz_ctx_t *ctx, uint32_t mask);
+
+/* The IDAT anchors of a host buffer (parity/debug): *out (atz_free) receives *n entries, position << 5 | 2,
+ * ascending.  An anchor at a: a >= 4, bytes 49 44 41 54 at a, the big-endian length L at a - 4 is below 2^31
+ * and a + 8 + L <= len.  mask as in atz_set_stitch. */
+int atz_stitch_anchors(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint32_t mask, uint64_t **out,
+                       uint64_t *n);
+
+/* The pieces of record `record` of the last atz_scan (before its atz_sweep): *offs and *lens (atz_free both)
+ * receive the file offset and the length of each of its *k pieces; *k = 0 for a record that is not stitched. */
+int atz_stitch_pieces(atz_ctx_t *ctx, uint64_t record, uint64_t **offs, uint64_t **lens, uint64_t *k);
 
 /* Batch of independent one-shot inflates of the given ranges of a host buffer (parity/debug):
  * status[i] in {0 end, 1 error, 2 need input}, consumed[i] = zlib total_in, produced[i] = total_out. */
