@@ -869,7 +869,9 @@ static constexpr int NLC = 286, NDC = 30, NBLC = 19, HEAPN = 2 * NLC + 1;
 static constexpr uint32_t LOOKMIN = 262;
 // fast-mode insertion ring, position mod 32768: queries are for chain nodes newer than p - MAX_DIST
 // (> p - 32768, so unambiguous); an older node only ever decides "no match within reach", which
-// holds whatever its (aliased) bit says, since every newer node is examined first
+// holds whatever its (aliased) bit says, since every newer node is examined first.  Unambiguous as long
+// as no position from p + 262 on is entered before p's nodes are read (p + 262 is p - MAX_DIST's bit at
+// windowBits 15): parse_fast enters a window's positions past its own chunks only after its checks.
 static constexpr uint32_t BITMAP_BITS = 32768;
 static constexpr uint32_t HOLE_SLOTS = HOLE_SLOTS_M;   // fast mode: latest skipped position per hash slot
 
@@ -2551,14 +2553,21 @@ struct TrialRun {
     const uint32_t last = P ? wb + 63u - (uint32_t)__builtin_clzll(P) : wb;
     // ---- insertion state of the path, then the check of its nodes
     t1 = STEP_CLOCK(); csec[2] += t1 - t0; t0 = t1;
-    if (qn > wb)
-      span_set(wb, qn, [&](uint32_t p, uint32_t& y, uint32_t& Ly) {
-        const uint32_t i = p - wb;   // huge for p < wb (such lanes are outside the span)
-        uint32_t yl = last - wb;
-        if (i < 64) yl = 63u - (uint32_t)__builtin_clzll(P & (~0ull >> (63 - i)));
-        y = wb + yl;
-        Ly = (uint32_t)__shfl((int)L, (int)yl, 64);
-      });
+    // Before the check only the window's own positions, to the end of their 64-position chunk: the nodes
+    // look back, never ahead.  The path can reach wb + 63 + 258, and in the insertion ring a position
+    // from x + 262 on is the same bit as x - 32506 and above: at windowBits 15 that is x - MAX_DIST, the
+    // hash head deflate_fast still walks, and the nodes just above it.  The rest of the span is entered
+    // once the path stands (a path that changes is covered again by the windows that follow).
+    auto cover_path = [&](uint32_t p, uint32_t& y, uint32_t& Ly) {
+      const uint32_t i = p - wb;   // huge for p < wb (such lanes are outside the span)
+      uint32_t yl = last - wb;
+      if (i < 64) yl = 63u - (uint32_t)__builtin_clzll(P & (~0ull >> (63 - i)));
+      y = wb + yl;
+      Ly = (uint32_t)__shfl((int)L, (int)yl, 64);
+    };
+    const uint32_t qown = qn < ((wb + 127u) & ~63u) ? qn : (wb + 127u) & ~63u;
+    static_assert(BITMAP_BITS >= (32768u - LOOKMIN) + 128u, "a window's own chunks alias no node within MAX_DIST");
+    if (qn > wb) span_set(wb, qown, cover_path);
 #if ATZ_STEP_SPLIT
     t1 = STEP_CLOCK(); csec[0] += t1 - t0; t0 = t1;   // (diagnostics: span_set counted with refill)
 #endif
@@ -2660,6 +2669,7 @@ struct TrialRun {
     t1 = STEP_CLOCK(); csec[3] += t1 - t0;
     if (state != ~0u) break;
     if (!restart && need) { state = TR_NEED_R; z.p = qn; break; }
+    if (!restart && qn > qown) span_set(qown, qn, cover_path);   // the path stands: the rest of its span
     q = qnext;
   }
   if (state == ~0u) {
