@@ -56,7 +56,7 @@ EXPORTS = ["atz_open", "atz_close", "atz_strerror", "atz_free", "atz_default_opt
            "atz_inflate_batch", "atz_deflate_bound", "atz_shard_scan", "atz_shard_sweep", "atz_shard_piece",
            "atz_shard_assemble", "atz_reconstruct_device", "atz_deflate_batch_ex", "atz_set_strategies",
            "atz_set_containers", "atz_container_anchors", "atz_set_stitch", "atz_stitch_anchors",
-           "atz_stitch_pieces"]
+           "atz_stitch_pieces", "atz_set_probe", "atz_probe_positions"]
 
 # zlib's strategy numbers (Z_FIXED, 4, is not supported); a strategy mask has bit k set for strategy k
 STRATEGIES = {"filtered": 1, "huffman": 2, "rle": 3}
@@ -103,6 +103,22 @@ def stitch_mask(names):
         if w not in STITCHERS:
             raise ValueError("unknown stitcher %r (known: %s)" % (w, ", ".join(sorted(STITCHERS))))
         mask |= 1 << STITCHERS[w]
+    return mask
+
+
+# what a probe mask makes the scan test every byte position for: bit number of each
+PROBES = {"deflate": 0}
+
+
+def probe_mask(names):
+    """("deflate",) or a comma-separated string -> atz_set_probe mask; ValueError on an unknown word."""
+    if isinstance(names, str):
+        names = [w for w in names.split(",") if w]
+    mask = 0
+    for w in names:
+        if w not in PROBES:
+            raise ValueError("unknown probe %r (known: %s)" % (w, ", ".join(sorted(PROBES))))
+        mask |= 1 << PROBES[w]
     return mask
 
 
@@ -182,6 +198,8 @@ def lib():
         L.atz_stitch_anchors.argtypes = L.atz_container_anchors.argtypes
         L.atz_stitch_pieces.argtypes = [C.c_void_p, u64, C.POINTER(C.POINTER(u64)), C.POINTER(C.POINTER(u64)),
                                         C.POINTER(u64)]
+        L.atz_set_probe.argtypes = [C.c_void_p, C.c_uint32]
+        L.atz_probe_positions.argtypes = [C.c_void_p, C.c_char_p, u64, C.POINTER(C.POINTER(u64)), C.POINTER(u64)]
         L.atz_deflate_bound.restype = u64
         L.atz_deflate_bound.argtypes = [u64, C.c_int, C.c_int]
         L.atz_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, u64, C.c_int, C.c_int, C.POINTER(u8p),
@@ -207,14 +225,18 @@ class Context:
     """One libatz_accel context (one GPU).  Mirrors the reference's programOptions (ATZData.h:7-35)."""
 
     def __init__(self, recomp_tresh=128, sizediff_tresh=128, shortcut_len=512, mismatch_tol=2,
-                 chunksize=524288, brute_window=False, device=-1, strategies=None, containers=None, stitch=None):
+                 chunksize=524288, brute_window=False, device=-1, strategies=None, containers=None, stitch=None,
+                 probe=None):
         """strategies: names of zlib strategies ("filtered", "rle", "huffman") to try on the streams the
         reference walk leaves unrecorded (an extension, off by default; None reads ATZ_STRATEGIES, a
         comma-separated list, as the CLI does).
         containers: "zip", "gzip": also look for the raw deflate bodies of ZIP entries and gzip members (an
         extension, off by default; None reads ATZ_CONTAINERS, a comma-separated list, as the CLI does).
         stitch: "png": also look for zlib streams split over the IDAT chunks of a PNG (an extension, off by
-        default; None reads ATZ_STITCH, a comma-separated list, as the CLI does)."""
+        default; None reads ATZ_STITCH, a comma-separated list, as the CLI does).
+        probe: "deflate": also test every byte position for the start of a raw deflate stream that no header or
+        container announces (an extension, off by default; None reads ATZ_PROBE, a comma-separated list, as the
+        CLI does)."""
         L = lib()
         self.o = Opts(recomp_tresh, sizediff_tresh, shortcut_len, mismatch_tol, chunksize, int(brute_window), device)
         if strategies is None:
@@ -226,6 +248,9 @@ class Context:
         if stitch is None:
             stitch = os.environ.get("ATZ_STITCH", "")
         smask = stitch_mask(stitch)
+        if probe is None:
+            probe = os.environ.get("ATZ_PROBE", "")
+        pmask = probe_mask(probe)
         self.h = C.c_void_p()
         _check(L.atz_open(C.byref(self.h), C.byref(self.o)))
         if mask:
@@ -234,6 +259,8 @@ class Context:
             _check(L.atz_set_containers(self.h, cmask))
         if smask:
             _check(L.atz_set_stitch(self.h, smask))
+        if pmask:
+            _check(L.atz_set_probe(self.h, pmask))
 
     def close(self):
         if self.h:
@@ -360,6 +387,16 @@ class Context:
         n = u64(0)
         _check(L.atz_stitch_anchors(self.h, data, len(data), mask, C.byref(p), C.byref(n)))
         out = [(p[i] >> 5, p[i] & 31) for i in range(n.value)]
+        L.atz_free(p)
+        return out
+
+    def probe_positions(self, data):
+        """The probe kernel's list for `data` (parity/debug): the surviving positions, ascending."""
+        L = lib()
+        p = C.POINTER(u64)()
+        n = u64(0)
+        _check(L.atz_probe_positions(self.h, data, len(data), C.byref(p), C.byref(n)))
+        out = [p[i] for i in range(n.value)]
         L.atz_free(p)
         return out
 

@@ -654,6 +654,11 @@ struct TrialSet {
   size_t base = 0;   // next free slot of d_trials / d_tres
 };
 
+struct ProbeList {   // the probe extension's survivors
+  std::vector<uint64_t> pos;   // the surviving positions, ascending
+  double kernel_ms = 0;        // k_probe_ordered, both passes
+};
+
 struct atz_ctx {
   KTimer kt;
   atz_opts_t o{};
@@ -683,6 +688,9 @@ struct atz_ctx {
   // (the sweep, the diff lists and the re-inflates read it); st_off / st_len: the pieces of the last scan's
   // stitched records, file offset and length each (Rec::p0, Rec::pk)
   uint32_t stitch_mask = 0;
+  // opt-in probe (atz_set_probe): bit 0 raw deflate streams whose first block is dynamic, which no header or
+  // container announces -- records of type 24 (raw, no hint), walked by raw_pass; 0: off
+  uint32_t probe_mask = 0;
   DBuf d_stitch;
   std::vector<uint64_t> st_off, st_len;
   // atz_sweep reports every stream's best ident, c, w, m as the reference computes them; the precompress
@@ -737,6 +745,9 @@ struct atz_ctx {
     int stage = 0;   // 1 scanned, 2 swept (piece in d_atz)
     std::chrono::steady_clock::time_point t0;
   } shard;
+  // the probe extension's list for the current scan (kept here, not in precompress_dev's frame, whose
+  // layout the sweep's threads share: with the mask off the call's stack is exactly what it was)
+  ProbeList probe;
 };
 
 // kind: 0 trial, 1 inflate, 2 chains, 3 other, 4 match tables
@@ -1365,21 +1376,20 @@ struct RawCand {
   uint64_t csize, usize;
 };
 
-// the anchors of the file, ascending: position << 5 | kind (count pass, host prefix, write pass)
-static int anchors_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint32_t mask, std::vector<uint64_t>& out) {
-  out.clear();
-  if (!mask || !F) return 0;
+// An ordered list kernel's two passes over the file (count pass, host prefix over the blocks, write pass):
+// launch(nb, seg, cnt, base, out, write) starts one pass of `name`; *kernel_ms: both passes' device time.
+template <class Launch>
+static int ordered_list_dev(atz_ctx* c, uint64_t F, const char* name, Launch launch, std::vector<uint64_t>& out,
+                            double* kernel_ms) {
   const uint64_t nb = std::max<uint64_t>(1, std::min<uint64_t>(8192, (F + 65535) / 65536));
   const uint64_t seg = ((F + nb - 1) / nb + 4095) & ~4095ull;
   if (int r = c->d_cnt.reserve(nb * 4 + 64)) return r;
   if (int r = c->d_hbase.reserve(nb * 8 + 64)) return r;
-  const auto t0 = std::chrono::steady_clock::now();
   const double other0 = c->stats.k_other_ms;
   kbeg(c, 3);
-  hipLaunchKernelGGL(k_anchors_ordered, dim3((uint32_t)nb), dim3(256), 0, c->st, d_file, F, seg, mask,
-                     c->d_cnt.as<uint32_t>(), nullptr, nullptr, 0);
+  launch((uint32_t)nb, seg, c->d_cnt.as<uint32_t>(), (const uint64_t*)nullptr, (uint64_t*)nullptr, 0);
   kend(c);
-  KCHECK("k_anchors_ordered");
+  KCHECK(name);
   std::vector<uint32_t> cnt(nb);
   HIPCHK(hipMemcpyAsync(cnt.data(), c->d_cnt.p, nb * 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
@@ -1390,18 +1400,31 @@ static int anchors_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint32_t m
     if (int r = upload(c, c->d_hbase, hb.data(), nb * 8)) return r;
     if (int r = c->d_pos.reserve(na * 8 + 64)) return r;
     kbeg(c, 3);
-    hipLaunchKernelGGL(k_anchors_ordered, dim3((uint32_t)nb), dim3(256), 0, c->st, d_file, F, seg, mask, nullptr,
-                       c->d_hbase.as<uint64_t>(), c->d_pos.as<uint64_t>(), 1);
+    launch((uint32_t)nb, seg, (uint32_t*)nullptr, c->d_hbase.as<uint64_t>(), c->d_pos.as<uint64_t>(), 1);
     kend(c);
-    KCHECK("k_anchors_ordered");
+    KCHECK(name);
     out.resize(na);
     HIPCHK(hipMemcpyAsync(out.data(), c->d_pos.p, na * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
   }
   kcollect(c);
+  *kernel_ms = c->stats.k_other_ms - other0;
+  return 0;
+}
+
+// the anchors of the file, ascending: position << 5 | kind
+static int anchors_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint32_t mask, std::vector<uint64_t>& out) {
+  out.clear();
+  if (!mask || !F) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  double kms = 0;
+  auto launch = [&](uint32_t nb, uint64_t seg, uint32_t* cnt, const uint64_t* base, uint64_t* dst, int write) {
+    hipLaunchKernelGGL(k_anchors_ordered, dim3(nb), dim3(256), 0, c->st, d_file, F, seg, mask, cnt, base, dst, write);
+  };
+  if (int r = ordered_list_dev(c, F, "k_anchors_ordered", launch, out, &kms)) return r;
   if (timing_on())
     std::fprintf(stderr, "atz: k_anchors_ordered: %llu anchors, kernels %.3f ms (both passes), host %.2f ms\n",
-                 (unsigned long long)na, c->stats.k_other_ms - other0, ms_since(t0));
+                 (unsigned long long)out.size(), kms, ms_since(t0));
   return 0;
 }
 
@@ -1648,6 +1671,72 @@ static int stitch_merge(atz_ctx* c, const uint8_t* d_file, uint64_t arena_cap, b
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Opt-in probe (atz_set_probe).  A raw deflate stream that no zlib header and no container
+// announces: k_probe_ordered tests every byte position of the file for a plausible dynamic-block start, one
+// raw k_inflate launch decodes the survivors that lie in no record made before, and one that decodes to its
+// end with PROBE_MIN_OUT bytes or more and meets no such record becomes a record of type 24 (raw, no hint),
+// which raw_pass walks as it walks a container's body.
+static constexpr uint64_t PROBE_MIN_OUT = 256;   // a dynamic header alone is 40-80 bytes: smaller bodies gain nothing
+static int probe_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, ProbeList& P) {
+  P.pos.clear();
+  P.kernel_ms = 0;
+  if (!F) return 0;
+  auto launch = [&](uint32_t nb, uint64_t seg, uint32_t* cnt, const uint64_t* base, uint64_t* dst, int write) {
+    hipLaunchKernelGGL(k_probe_ordered, dim3(nb), dim3(256), 0, c->st, d_file, F, seg, cnt, base, dst, write);
+  };
+  return ordered_list_dev(c, F, "k_probe_ordered", launch, P.pos, &P.kernel_ms);
+}
+
+// The probe's records merged into c->recs (every record made before, complete, in file order): survivors
+// inside a record's hull are not decoded (every byte-aligned block start of a known stream would be one);
+// the rest are decoded to the end of the file (outputs in the scan's arena behind the earlier candidates';
+// fresh_arena: no job ran before), accepted by status and output size, dropped where they meet a record made
+// before, taken greedily in ascending offset.  c->recs keeps its capacity.
+static int probe_merge(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint64_t arena_cap, bool fresh_arena,
+                       const ProbeList& P) {
+  auto tm_ = std::chrono::steady_clock::now();
+  const std::vector<Rec>& ref = c->recs;
+  std::vector<InfJob> jobs;
+  {
+    size_t i = 0;
+    for (const uint64_t p : P.pos) {
+      while (i < ref.size() && ref[i].offset + ref[i].hull() <= p) i++;
+      if (i < ref.size() && ref[i].offset <= p) continue;
+      jobs.push_back({p, F - p, ARENA_OUT, ARENA_SLOT});
+    }
+  }
+  const double infl0 = c->stats.k_inflate_ms;
+  std::vector<InfRes> res;
+  if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, arena_cap, false, fresh_arena, true)) return r;
+  std::vector<Rec> merged;
+  merged.reserve(ref.size() + 16);
+  size_t i = 0, accepted = 0, kept = 0;
+  uint64_t end = 0;
+  for (size_t k = 0; k < jobs.size(); k++) {
+    const InfRes& r = res[k];
+    if (r.status != INF_END || r.produced < PROBE_MIN_OUT || r.produced >= (1ull << 31)) continue;
+    accepted++;
+    const uint64_t lo = jobs[k].in_off, hi = lo + r.consumed;
+    const auto it = std::lower_bound(ref.begin(), ref.end(), hi, [](const Rec& x, uint64_t v) { return x.offset < v; });
+    if (it != ref.begin() && (it - 1)->offset + (it - 1)->hull() > lo) continue;
+    if (lo < end) continue;   // starts inside the probe record kept before it
+    end = hi;
+    while (i < ref.size() && ref[i].offset < lo) merged.push_back(ref[i++]);
+    merged.push_back(Rec{lo, r.consumed, r.produced, 24 /* raw, hint none */, 0, r.arena_off});
+    kept++;
+  }
+  while (i < ref.size()) merged.push_back(ref[i++]);
+  if (timing_on())
+    std::fprintf(stderr, "atz: k_probe_ordered: %zu survivors, kernels %.3f ms (both passes), %zu decoded, "
+                 "k_inflate %.3f ms, %zu accepted, %zu kept\n", P.pos.size(), P.kernel_ms, jobs.size(),
+                 c->stats.k_inflate_ms - infl0, accepted, kept);
+  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
+  if (kept) c->recs.assign(merged.begin(), merged.end());
+  TMARK("scan: probe candidates");
+  return 0;
+}
+
 // the last four bytes of record r's stream (its Adler-32 trailer, big-endian) from the host copy h: a
 // stitched record's may straddle its pieces
 static uint32_t rec_trailer(const atz_ctx* c, const Rec& r, const uint8_t* h) {
@@ -1680,11 +1769,17 @@ static int scan_impl(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64
   if (int r = anchors_dev(c, d_file, F, ext_anchor_mask(c), anchors)) return r;
   raw_candidates(h, F, anchors, rc);
   stitch_candidates(h, anchors, sp);
+  ProbeList& pl = c->probe;
+  pl.pos.clear();
+  if (c->probe_mask)
+    if (int r = probe_dev(c, d_file, F, pl)) return r;
   c->st_off.clear(); c->st_len.clear();
-  c->recs.reserve(S.max_records() + rc.size() + sp.cands.size());
+  c->recs.reserve(S.max_records() + rc.size() + sp.cands.size() + pl.pos.size());
   if (int r = scan_piece(c, h, d_file, S, 0, (uint32_t)S.chunks.size())) return r;
   if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), rc)) return r;
   if (int r = stitch_merge(c, d_file, S.arena_cap, S.fjobs.empty() && rc.empty(), sp)) return r;
+  if (c->probe_mask)
+    if (int r = probe_merge(c, d_file, F, S.arena_cap, S.fjobs.empty() && rc.empty() && sp.cands.empty(), pl)) return r;
   c->stats.scan_ms = ms_since(t0);
   return 0;
 }
@@ -3736,7 +3831,7 @@ static void raw_list(std::vector<uint32_t>& l, int type) {
     for (int cl : lo[type - 24]) l.push_back((1u << 28) | pk(cl, 15, m));
 }
 static int raw_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
-  return c->cont_mask ? ext_pass(c, d_file, ss, true) : 0;
+  return (c->cont_mask || c->probe_mask) ? ext_pass(c, d_file, ss, true) : 0;
 }
 
 // the sweep of every record of the context (atz_sweep)
@@ -3905,7 +4000,10 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
     raw_candidates(h, F, anchors, raw_cands);
     stitch_candidates(h, anchors, stitch_plan);
   }
-  const size_t n_max = S.max_records() + raw_cands.size() + stitch_plan.cands.size();
+  if (c->probe_mask)   // (the probe extension's survivors, likewise: each may become a record)
+    if (int r = probe_dev(c, d_file, F, c->probe)) return r;
+  const size_t n_max = S.max_records() + raw_cands.size() + stitch_plan.cands.size() +
+                       (c->probe_mask ? c->probe.pos.size() : 0);
   c->recs.reserve(n_max);
   std::vector<StreamState>& ss = c->ss_keep;
   SweepRun R;
@@ -3931,8 +4029,9 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   });
   struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join_begin{t_begin};
   double scan_busy = ms_since(t0);
-  // (with a container or stitch mask the added records need the reference's final ones: scan, merge, then sweep)
-  const bool spec = P == 1 && spec_cont_on() && !ext_anchor_mask(c);
+  // (with a container, stitch or probe mask the added records need the reference's final ones: scan, merge,
+  // then sweep)
+  const bool spec = P == 1 && spec_cont_on() && !ext_anchor_mask(c) && !c->probe_mask;
   if (spec) {
     // The first continuations of pending streams (each a decode of the stream from its header through
     // the chunk boundary) are latency-bound: one small launch, 15-30 ms.  The records do not wait for
@@ -3999,6 +4098,10 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
     if (int r = scan_piece(c, h, d_file, S, ja, jb)) return r;
     if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), raw_cands)) return r;
     if (int r = stitch_merge(c, d_file, S.arena_cap, S.fjobs.empty() && raw_cands.empty(), stitch_plan)) return r;
+    if (c->probe_mask)
+      if (int r = probe_merge(c, d_file, F, S.arena_cap,
+                              S.fjobs.empty() && raw_cands.empty() && stitch_plan.cands.empty(), c->probe))
+        return r;
     if (p == 0) {
       t_begin.join();
       if (rc_begin) return rc_begin;
@@ -4950,6 +5053,29 @@ int atz_stitch_anchors(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint32_t
   });
 }
 
+int atz_set_probe(atz_ctx_t* c, uint32_t mask) {
+  if (!c || (mask & ~1u)) return ATZ_E_ARG;   // bit 0: raw deflate starts whose first block is dynamic
+  c->probe_mask = mask;
+  c->scan_valid = false;
+  return ATZ_OK;
+}
+
+int atz_probe_positions(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint64_t** out, uint64_t* n) {
+  return guarded([&]() -> int {
+    (void)hipGetLastError();
+    if (!c || (!file && len) || !out || !n) return ATZ_E_ARG;
+    c->scan_valid = false; c->shard.stage = 0;   // d_file is replaced
+    if (int r = upload(c, c->d_file, file, len)) return r;
+    ProbeList pl;
+    if (int r = probe_dev(c, c->d_file.as<uint8_t>(), len, pl)) return r;
+    *out = (uint64_t*)std::malloc((pl.pos.size() + 1) * 8);
+    if (!*out) return ATZ_E_NOMEM;
+    if (!pl.pos.empty()) std::memcpy(*out, pl.pos.data(), pl.pos.size() * 8);
+    *n = pl.pos.size();
+    return ATZ_OK;
+  });
+}
+
 int atz_stitch_pieces(atz_ctx_t* c, uint64_t record, uint64_t** offs, uint64_t** lens, uint64_t* k) {
   return guarded([&]() -> int {
     if (!c || !offs || !lens || !k || !c->scan_valid || record >= c->recs.size()) return ATZ_E_ARG;
@@ -4990,7 +5116,7 @@ int atz_shard_scan(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, u
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !blob || !blob_len || world < 1 || rank < 0 || rank >= world) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask || c->stitch_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
+    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
     dev_mark_call();   // (the peak runs on through atz_shard_sweep, whose stats report it)
     std::vector<uint64_t> b;
     if (int r = shard_scan_impl(c, d_file, h_file, len, rank, world, b)) { c->shard.stage = 0; return r; }
@@ -5008,7 +5134,7 @@ int atz_shard_sweep(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, 
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !piece_len || !recomp_flags || !n_flags || !n_recomp) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask || c->stitch_mask) return ATZ_E_ARG;
+    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask) return ATZ_E_ARG;
     std::vector<uint8_t> f;
     if (int r = shard_sweep_impl(c, d_file, h_file, len, blobs, blob_lens, world, f, n_recomp)) {
       c->shard.stage = 0;

@@ -270,6 +270,95 @@ __global__ __launch_bounds__(256) void k_anchors_ordered(const uint8_t* __restri
   if (!write && t == 0) cnt[blockIdx.x] = total;
 }
 
+// The probe (the opt-in probe extension): does a raw deflate stream whose first block is
+// dynamic plausibly start at a position?  Bits LSB-first from the position's byte:
+//   1. bits 1-2 = 2 (BTYPE dynamic; BFINAL either);  2. HLIT (3-7) <= 29 and HDIST (8-12) <= 29;
+//   3. with nc = (bits 13-16) + 4, the 17 + 3 nc header bits lie inside the file;
+//   4. the nc 3-bit code-length-code lengths l != 0 sum to a complete code, sum 2^(7 - l) = 128.
+// probe_cheap is conditions 1-2 on the first two bytes x; probe_kraft is 3-4 on bytes 0-7 (lo) and 8-11 (hi)
+// of a position with `left` file bytes from it on (left >= 4: the least a header needs, so bits 13-16 are
+// file bytes).  Bytes at or past the end are zero in lo / hi and never decide: condition 3 comes first.
+__device__ __forceinline__ bool probe_cheap(uint32_t x) {
+  return ((x >> 1) & 3u) == 2u && ((x >> 3) & 31u) <= 29u && ((x >> 8) & 31u) <= 29u;
+}
+__device__ __forceinline__ bool probe_kraft(uint64_t lo, uint32_t hi, uint64_t left) {
+  const uint32_t nc = ((uint32_t)(lo >> 13) & 15u) + 4u;
+  if ((uint64_t)((17u + 3u * nc + 7u) >> 3) > left) return false;
+  uint64_t u = (lo >> 17) | ((uint64_t)hi << 47);   // the 3-bit fields, from bit 0 on
+  u &= (1ull << (3u * nc)) - 1ull;                  // (nc <= 19: 57 bits) fields past nc count as length 0
+  uint32_t sum = 0;
+#pragma unroll
+  for (int i = 0; i < 19; i++) sum += (0x80u >> ((uint32_t)(u >> (3 * i)) & 7u)) & 0x7fu;   // l = 0 adds nothing
+  return sum == 128u;
+}
+
+// k_headers_ordered's two passes for the probe: count mode writes the block's total to cnt[b]; write mode
+// writes the surviving positions in file order from base[b] on.  A lane owns the 16 positions of its 16-byte
+// load and holds the 16 bytes after them too (a header is at most 10 bytes); both loads stop at the file's
+// end.  The 13-bit test runs on all 16 positions into a mask; the Kraft sum only where its bit is set.
+__global__ __launch_bounds__(256) void k_probe_ordered(const uint8_t* __restrict__ f, uint64_t n, uint64_t seg,
+                                                       uint32_t* __restrict__ cnt, const uint64_t* __restrict__ base,
+                                                       uint64_t* __restrict__ out, int write) {
+  __shared__ uint32_t wsum[4];
+  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const uint64_t s0 = (uint64_t)blockIdx.x * seg;
+  const uint64_t s1 = s0 + seg < n ? s0 + seg : n;
+  uint64_t o = write ? base[blockIdx.x] : 0;
+  uint32_t total = 0;
+  for (uint64_t sb = s0; sb < s1; sb += 4096) {
+    const uint64_t p = sb + (uint64_t)t * 16;
+    uint32_t hits = 0;
+    if (p < s1) {
+      uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (p + 32 <= n) {
+        const uint4 a = *reinterpret_cast<const uint4*>(f + p);
+        const uint4 b = *reinterpret_cast<const uint4*>(f + p + 16);
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+      } else {
+        for (int k = 0; k < 32; k++)
+          if (p + k < n) d[k >> 2] |= (uint32_t)f[p + k] << (8 * (k & 3));
+      }
+      uint32_t m = 0;
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        const uint32_t x = __funnelshift_r(d[k >> 2], d[(k >> 2) + 1], 8 * (k & 3));
+        m |= (uint32_t)(probe_cheap(x) && p + k < s1 && p + k + 4 <= n) << k;
+      }
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        if (m & (1u << k)) {
+          const int j = k >> 2, s = 8 * (k & 3);
+          const uint32_t x0 = __funnelshift_r(d[j], d[j + 1], s), x1 = __funnelshift_r(d[j + 1], d[j + 2], s);
+          const uint32_t x2 = __funnelshift_r(d[j + 2], d[j + 3], s);
+          if (probe_kraft(((uint64_t)x1 << 32) | x0, x2, n - (p + k))) hits |= 1u << k;
+        }
+      }
+    }
+    const uint32_t c = __popc(hits);
+    uint32_t incl = c;
+    for (int e = 1; e < 64; e <<= 1) {
+      const uint32_t y = __shfl_up(incl, e, 64);
+      if ((int)lane >= e) incl += y;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint32_t before = 0, step = 0;
+    for (uint32_t k = 0; k < 4; k++) { const uint32_t y = wsum[k]; if (k < w) before += y; step += y; }
+    __syncthreads();
+    if (write) {
+      uint64_t q = o + before + incl - c;
+      while (hits) {
+        const int k = __ffs(hits) - 1;
+        hits &= hits - 1;
+        out[q++] = p + k;
+      }
+    }
+    o += step;
+    total += step;
+  }
+  if (!write && t == 0) cnt[blockIdx.x] = total;
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_inflate: one wavefront per job, everything inlined into the kernel so the decoder state stays
 // in (wave-uniform) SGPRs -- a by-reference state struct crossing a call would live in scratch.

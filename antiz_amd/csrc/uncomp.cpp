@@ -483,10 +483,26 @@ int main(int argc, char* argv[]) {
       }
     }
   }
+  // ATZ_PROBE=deflate (not a reference flag): also test every byte position for the start of a raw deflate
+  // stream that no header or container announces (atz_set_probe)
+  uint32_t probe = 0;
+  if (const char* e = std::getenv("ATZ_PROBE")) {
+    std::stringstream words(e);
+    std::string w;
+    while (std::getline(words, w, ',')) {
+      if (w.empty()) continue;
+      if (w == "deflate") probe |= 1u << 0;
+      else {
+        std::cerr << "Error Encountered: " << "ATZ_PROBE: unknown probe " << w << std::endl;
+        return done(1);
+      }
+    }
+  }
   if (open_ctx()) return done(255);
   if (strategies && atz_set_strategies(ctx, strategies) != 0) return done(255);
   if (containers && atz_set_containers(ctx, containers) != 0) return done(255);
   if (stitch && atz_set_stitch(ctx, stitch) != 0) return done(255);
+  if (probe && atz_set_probe(ctx, probe) != 0) return done(255);
   uint8_t* atz = nullptr;
   uint64_t al = 0;
   atz_stats_t st;

@@ -17,9 +17,10 @@
  *   atz_deflate     one deflateInit2/deflate(Z_FINISH)/deflateEnd              main.cpp:976-1003
  *   atz_shard_*     the precompress of one file split over several GPUs (new: the reference is
  *                   single-threaded)
- * Three opt-in extensions, each off by default and leaving every output as the reference's while off:
+ * Four opt-in extensions, each off by default and leaving every output as the reference's while off:
  *   atz_set_strategies  zlib strategy trials ("ATZ\2"), atz_set_containers  raw deflate in ZIP / gzip ("ATZ\3"),
- *   atz_set_stitch      zlib streams split over PNG IDAT chunks ("ATZ\4")
+ *   atz_set_stitch      zlib streams split over PNG IDAT chunks ("ATZ\4"),
+ *   atz_set_probe       raw deflate streams that nothing announces ("ATZ\3")
  */
 #ifndef ATZ_ACCEL_H
 #define ATZ_ACCEL_H
@@ -49,7 +50,8 @@ typedef struct {
     uint64_t infl_len;   /* inflatedLength */
     int32_t  type;       /* offsetType 0..23; 24 + hint for a raw deflate body behind a ZIP or gzip header
                             (only with atz_set_containers; hint 0 none, 1 fast, 2 max): offset is the
-                            body's first byte, comp_len the body's length */
+                            body's first byte, comp_len the body's length; 24 also for a raw stream the probe
+                            found (only with atz_set_probe) */
     uint32_t flags;      /* bit0: recorded through a chunk-boundary continuation; bit1: the first block is
                             dynamic and codes matches but none of length 3-5 (a Z_FILTERED-like stream: the
                             multi-GPU split's cost hint, not part of the reference's record); bits 2-5:
@@ -215,6 +217,23 @@ int atz_stitch_anchors(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint32
 /* The pieces of record `record` of the last atz_scan (before its atz_sweep): *offs and *lens (atz_free both)
  * receive the file offset and the length of each of its *k pieces; *k = 0 for a record that is not stitched. */
 int atz_stitch_pieces(atz_ctx_t *ctx, uint64_t record, uint64_t **offs, uint64_t **lens, uint64_t *k);
+
+/* Opt-in probe (an extension: raw deflate streams that no zlib header and no container announces).  mask bit
+ * 0: streams whose first block is dynamic; 0, the default, is off and leaves every output as what a context
+ * without this mask writes.  With the mask, the scan tests every byte position p of the file, reading bits
+ * LSB-first from byte p: bits 1-2 = 2 (BTYPE dynamic), HLIT (bits 3-7) <= 29, HDIST (bits 8-12) <= 29, with nc
+ * = (bits 13-16) + 4 all 17 + 3 nc header bits inside the file, and the nc 3-bit code-length-code lengths l != 0
+ * a complete code (sum of 2^(7 - l) = 128).  A surviving position outside every record made before (the
+ * reference's, the container extension's, a stitched record's hull) is decoded as a raw stream to the end of
+ * the file; one that ends with 256 <= output < 2^31 bytes, meets no such record and does not start inside the
+ * probe record kept before it becomes a record of atz_cand_t.type 24 (raw, no hint), walked, reported and
+ * written ("ATZ\3") exactly as a container's body is.  Streams whose first block is stored or fixed are not
+ * looked for.  The atz_shard_* calls return ATZ_E_ARG on a context with a mask. */
+int atz_set_probe(atz_ctx_t *ctx, uint32_t mask);
+
+/* The probe kernel's list for a host buffer (parity/debug): *out (atz_free) receives the *n surviving
+ * positions, ascending, as plain positions. */
+int atz_probe_positions(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint64_t **out, uint64_t *n);
 
 /* Batch of independent one-shot inflates of the given ranges of a host buffer (parity/debug):
  * status[i] in {0 end, 1 error, 2 need input}, consumed[i] = zlib total_in, produced[i] = total_out. */
