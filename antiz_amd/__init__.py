@@ -56,7 +56,7 @@ EXPORTS = ["atz_open", "atz_close", "atz_strerror", "atz_free", "atz_default_opt
            "atz_inflate_batch", "atz_deflate_bound", "atz_shard_scan", "atz_shard_sweep", "atz_shard_piece",
            "atz_shard_assemble", "atz_reconstruct_device", "atz_deflate_batch_ex", "atz_set_strategies",
            "atz_set_containers", "atz_container_anchors", "atz_set_stitch", "atz_stitch_anchors",
-           "atz_stitch_pieces", "atz_set_probe", "atz_probe_positions"]
+           "atz_stitch_pieces", "atz_set_probe", "atz_probe_positions", "atz_set_deflaters"]
 
 # zlib's strategy numbers (Z_FIXED, 4, is not supported); a strategy mask has bit k set for strategy k
 STRATEGIES = {"filtered": 1, "huffman": 2, "rle": 3}
@@ -119,6 +119,22 @@ def probe_mask(names):
         if w not in PROBES:
             raise ValueError("unknown probe %r (known: %s)" % (w, ", ".join(sorted(PROBES))))
         mask |= 1 << PROBES[w]
+    return mask
+
+
+# deflater families beside zlib's that a deflater mask adds to the raw walk: bit number of each
+DEFLATERS = {"gnu": 0}
+
+
+def deflater_mask(names):
+    """("gnu",) or a comma-separated string -> atz_set_deflaters mask; ValueError on an unknown word."""
+    if isinstance(names, str):
+        names = [w for w in names.split(",") if w]
+    mask = 0
+    for w in names:
+        if w not in DEFLATERS:
+            raise ValueError("unknown deflater %r (known: %s)" % (w, ", ".join(sorted(DEFLATERS))))
+        mask |= 1 << DEFLATERS[w]
     return mask
 
 
@@ -200,6 +216,7 @@ def lib():
                                         C.POINTER(u64)]
         L.atz_set_probe.argtypes = [C.c_void_p, C.c_uint32]
         L.atz_probe_positions.argtypes = [C.c_void_p, C.c_char_p, u64, C.POINTER(C.POINTER(u64)), C.POINTER(u64)]
+        L.atz_set_deflaters.argtypes = [C.c_void_p, C.c_uint32]
         L.atz_deflate_bound.restype = u64
         L.atz_deflate_bound.argtypes = [u64, C.c_int, C.c_int]
         L.atz_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, u64, C.c_int, C.c_int, C.POINTER(u8p),
@@ -226,7 +243,7 @@ class Context:
 
     def __init__(self, recomp_tresh=128, sizediff_tresh=128, shortcut_len=512, mismatch_tol=2,
                  chunksize=524288, brute_window=False, device=-1, strategies=None, containers=None, stitch=None,
-                 probe=None):
+                 probe=None, deflaters=None):
         """strategies: names of zlib strategies ("filtered", "rle", "huffman") to try on the streams the
         reference walk leaves unrecorded (an extension, off by default; None reads ATZ_STRATEGIES, a
         comma-separated list, as the CLI does).
@@ -236,7 +253,9 @@ class Context:
         default; None reads ATZ_STITCH, a comma-separated list, as the CLI does).
         probe: "deflate": also test every byte position for the start of a raw deflate stream that no header or
         container announces (an extension, off by default; None reads ATZ_PROBE, a comma-separated list, as the
-        CLI does)."""
+        CLI does).
+        deflaters: "gnu": the raw records' walk (containers, probe) also tries the deflater of GNU gzip and Info-ZIP's
+        zip (an extension, off by default; None reads ATZ_DEFLATERS, a comma-separated list, as the CLI does)."""
         L = lib()
         self.o = Opts(recomp_tresh, sizediff_tresh, shortcut_len, mismatch_tol, chunksize, int(brute_window), device)
         if strategies is None:
@@ -251,6 +270,9 @@ class Context:
         if probe is None:
             probe = os.environ.get("ATZ_PROBE", "")
         pmask = probe_mask(probe)
+        if deflaters is None:
+            deflaters = os.environ.get("ATZ_DEFLATERS", "")
+        dmask = deflater_mask(deflaters)
         self.h = C.c_void_p()
         _check(L.atz_open(C.byref(self.h), C.byref(self.o)))
         if mask:
@@ -261,6 +283,8 @@ class Context:
             _check(L.atz_set_stitch(self.h, smask))
         if pmask:
             _check(L.atz_set_probe(self.h, pmask))
+        if dmask:
+            _check(L.atz_set_deflaters(self.h, dmask))
 
     def close(self):
         if self.h:
@@ -411,9 +435,11 @@ class Context:
         L.atz_free(pl)
         return out
 
-    def deflate(self, data, clevel, window, memlevel, strategy=0, raw=False):
-        if strategy or raw:
-            return self.deflate_batch(data, [(0, len(data), clevel, window, memlevel, strategy, raw)])[0]
+    def deflate(self, data, clevel, window, memlevel, strategy=0, raw=False, deflater=None):
+        """deflater: None zlib 1.2.8's; "gnu" GNU gzip's and Info-ZIP's (raw, window 15, strategy 0, level 1-9 only;
+        memlevel is ignored)."""
+        if strategy or raw or deflater:
+            return self.deflate_batch(data, [(0, len(data), clevel, window, memlevel, strategy, raw, deflater)])[0]
         L = lib()
         cap = L.atz_deflate_bound(len(data), 10, 1) + 1024
         out = C.create_string_buffer(cap)
@@ -422,14 +448,15 @@ class Context:
         return out.raw[:n.value]
 
     def deflate_batch(self, buf, items):
-        """items: list of (offset, length, clevel, window, memlevel[, strategy[, raw]]) over `buf`; returns list of
-        bytes.  raw: the deflate body alone (no zlib header, no Adler-32 trailer)."""
+        """items: list of (offset, length, clevel, window, memlevel[, strategy[, raw[, deflater]]]) over `buf`; returns
+        list of bytes.  raw: the deflate body alone (no zlib header, no Adler-32 trailer).  deflater: see deflate()."""
         L = lib()
         k = len(items)
         offs = (u64 * max(k, 1))(*[it[0] for it in items])
         lens = (u64 * max(k, 1))(*[it[1] for it in items])
-        ex = any((len(it) > 5 and it[5]) or (len(it) > 6 and it[6]) for it in items)
-        prm = (C.c_uint32 * max(k, 1))(*[((1 << 28) if len(it) > 6 and it[6] else 0) |
+        ex = any(any(it[5:8]) for it in items)
+        prm = (C.c_uint32 * max(k, 1))(*[((deflater_mask((it[7],)) << 29) if len(it) > 7 and it[7] else 0) |
+                                         ((1 << 28) if len(it) > 6 and it[6] else 0) |
                                          ((it[5] << 24) if len(it) > 5 else 0) | (it[2] << 16) | (it[3] << 8) | it[4]
                                          for it in items])
         caps = [L.atz_deflate_bound(it[1], 10, 1) + 64 for it in items]

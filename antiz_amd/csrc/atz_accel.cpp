@@ -499,6 +499,7 @@ struct KTimer {   // HIP events bracketing kernel launches on the library stream
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
   std::vector<int> kind;
   std::vector<hipEvent_t> pool;
+  double gnu_ms = 0;   // kind 5: the GNU-family trial kernels' share of k_trial_ms (ATZ_TIMING's raw pass line)
   hipEvent_t get() {
     if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
     hipEvent_t e; (void)hipEventCreate(&e); return e;
@@ -691,6 +692,8 @@ struct atz_ctx {
   // opt-in probe (atz_set_probe): bit 0 raw deflate streams whose first block is dynamic, which no header or
   // container announces -- records of type 24 (raw, no hint), walked by raw_pass; 0: off
   uint32_t probe_mask = 0;
+  // opt-in deflater families for the raw walk (atz_set_deflaters): bit 0 GNU gzip's and Info-ZIP's; 0: zlib's only
+  uint32_t defl_mask = 0;
   DBuf d_stitch;
   std::vector<uint64_t> st_off, st_len;
   // atz_sweep reports every stream's best ident, c, w, m as the reference computes them; the precompress
@@ -750,7 +753,7 @@ struct atz_ctx {
   ProbeList probe;
 };
 
-// kind: 0 trial, 1 inflate, 2 chains, 3 other, 4 match tables
+// kind: 0 trial, 1 inflate, 2 chains, 3 other, 4 match tables, 5 GNU-family trial (counted as a trial too)
 template <class C>
 static void kbeg(C* c, int kind, hipStream_t st = nullptr) {
   hipEvent_t a = c->kt.get(), b = c->kt.get();
@@ -767,6 +770,7 @@ static void kcollect(C* c) {
     float ms = 0;
     (void)hipEventElapsedTime(&ms, c->kt.pending[i].first, c->kt.pending[i].second);
     switch (c->kt.kind[i]) {
+      case 5: c->kt.gnu_ms += ms; [[fallthrough]];
       case 0: c->stats.k_trial_ms += ms; c->stats.k_trial_launches++; break;
       case 1: c->stats.k_inflate_ms += ms; c->stats.k_inflate_launches++; break;
       case 2: c->stats.k_chains_ms += ms; c->stats.k_chains_launches++; break;
@@ -2274,10 +2278,14 @@ static uint32_t mw_cap_for(size_t n_streams) {
 static bool mw_trial(const Pipe* c, int kind, uint32_t memlevel) { return kind != 0 && memlevel <= c->mw_cap; }
 // the kernel a trial of kind k runs on: bit 0 multi-wave, bits 1-2 its strategy (Trial::host & TH_STRAT:
 // 1 Z_FILTERED on the slow kind, 3 Z_RLE / 2 Z_HUFFMAN_ONLY on the table-less kind 0)
+// bit 3: the GNU deflater family (Trial::host & TH_GNU), always single-wave
 static uint32_t trial_variant(const Pipe* c, int k, const Trial& t) {
+  if (t.host & TH_GNU) return 8u;
   return (mw_trial(c, k, t.memlevel) ? 1u : 0u) | ((t.host & TH_STRAT) << 1);
 }
+// (memlevel 0: a GNU-family trial, whose blocks hold up to 32 767 symbols whatever the stream's tables)
 static uint64_t sym_words(const Pipe* c, int kind, uint32_t memlevel, uint64_t n) {   // symbol buffer of a trial (u32 units)
+  if (!memlevel) return 32768 + 64;
   return (mw_trial(c, kind, memlevel) ? n + 64 : 0) + (1ull << (memlevel + 6)) + 64;
 }
 // The trials of one batch on a pipe, by kind (0 stored, 1 fast, 2 slow levels), each with its slice of the
@@ -2287,14 +2295,16 @@ struct TrialBatch {
   uint64_t out_tot = 0, sym_tot = 0;
   // A trial of stream s (len inflated bytes) at (level, window, memLevel) under zlib strategy strat.
   // Z_RLE and Z_HUFFMAN_ONLY ignore the level and read no tables (the stored kind's kernels); Z_FILTERED
-  // only changes deflate_slow, so on levels 1-3 it is the default strategy.  Returns (kind, index in tr[kind]).
+  // only changes deflate_slow, so on levels 1-3 it is the default strategy.  m == 0: a GNU-family trial (level
+  // 1-9, raw, default strategy: the callers' checks), which parses at memLevel 8 and carries TH_GNU.
+  // Returns (kind, index in tr[kind]).
   std::pair<int, uint32_t> add(const Pipe* c, uint32_t s, uint64_t len, int cl, int w, int m, uint32_t strat,
                                uint8_t mode, uint64_t best_ident) {
     if (strat == 1 && cl < 4) strat = 0;
     const int kind = cl == 0 || strat >= 2 ? 0 : cl <= 3 ? 1 : 2;
     Trial t{};
-    t.stream = s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)m;
-    t.mode = mode; t.host = strat;
+    t.stream = s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)(m ? m : 8);
+    t.mode = mode; t.host = strat | (m ? 0u : (uint32_t)TH_GNU);
     t.best_ident = best_ident;
     t.out_off = out_tot; t.out_cap = bound(len, w, m) + 64;
     out_tot += (t.out_cap + 255) & ~255ull;
@@ -2330,7 +2340,7 @@ static void trials_order(atz_ctx* x, const Pipe* c, std::vector<Trial>* in, Tria
     bool strat = false;   // strategy trials among them
     for (size_t q = 0; q < n; q++) {
       const Trial& t = in[k][q];
-      strat |= (t.host & TH_STRAT) != 0;
+      strat |= (t.host & (TH_STRAT | TH_GNU)) != 0;
       const uint64_t w = x->recs[t.stream].infl_len * (uint64_t)(k == 1 ? 3 : 1) * (uint64_t)(10 - t.memlevel) *
                          (uint64_t)((t.mode & TM_REPLAY) ? 1 : 4);   // replays skip the match walks
       const uint64_t mw = k != 0 && t.memlevel <= mwm;
@@ -2349,7 +2359,7 @@ static void trials_order(atz_ctx* x, const Pipe* c, std::vector<Trial>* in, Tria
         return ma != mb ? ma : key[a] > key[b];
       });
     }
-    // strategy trials run on kernels of their own: one run per (multi-wave, strategy), in the order above
+    // strategy and GNU-family trials run on kernels of their own: one run per variant, in the order above
     if (strat)
       std::stable_sort(S.perm[k].begin(), S.perm[k].end(), [&](uint32_t a, uint32_t b) {
         return trial_variant(c, k, in[k][a]) < trial_variant(c, k, in[k][b]);
@@ -2376,6 +2386,8 @@ static int trials_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, const SweepO
       {2, 0, false, k_trial_slow, "k_trial_slow"},
       {2, 1, true, k_trial_slow_filt_mw, "k_trial_slow_filt"},
       {2, 1, false, k_trial_slow_filt, "k_trial_slow_filt"},
+      {1, 4, false, k_trial_fast_gnu, "k_trial_fast_gnu"},   // (strat 4: trial_variant's bit 3, the GNU family)
+      {2, 4, false, k_trial_slow_gnu, "k_trial_slow_gnu"},
   };
   for (size_t i = 0; i < cnt; i++)   // a waiting trial or a duplicate never reaches a launch
     if (h[i].host & (TH_WAITS | TH_DUP)) return ATZ_E_INTERNAL;
@@ -2402,7 +2414,7 @@ static int trials_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, const SweepO
     A.adler = x->d_adler.as<uint32_t>(); A.o = so; A.ntrials = (uint32_t)n1;
     A.stopj = c->stopj_cur;
     dim3 g((uint32_t)n1), b(mw ? MW_THREADS : 64);
-    kbeg(c, 0);
+    kbeg(c, variant & 8u ? 5 : 0);
     hipLaunchKernelGGL(kn->fn, g, b, 0, c->st, A);
     kend(c);
     KCHECK(kn->name);
@@ -3691,7 +3703,9 @@ static void strategy_list(std::vector<uint32_t>& l, int type, uint32_t mask) {
 // batch builds the bucket tables its filtered trials read, as deflate_dev does).  A stream the pass
 // records gets clevel = strategy << 4 | level; the others keep what the reference walk left.
 // raw: the same pass over the container extension's records (raw_list; TM_RAW trials), see raw_pass.
-static void raw_list(std::vector<uint32_t>& l, int type);
+static void raw_list(std::vector<uint32_t>& l, int type, uint32_t defl_mask);
+// the memLevel whose bucket and match tables a list entry's trial reads (memLevel 0, a GNU candidate: 8)
+static int tab_memlevel(uint32_t q) { return (q & 0xff) ? (int)(q & 0xff) : 8; }
 static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss, bool raw) {
   const auto t0 = std::chrono::steady_clock::now();
   const size_t n = ss.size();
@@ -3708,7 +3722,7 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
   size_t longest = 0;
   for (size_t s = 0; s < n; s++) {
     if (ss[s].recomp || c->recs[s].infl_len >= (1ull << 31)) continue;
-    if (raw) raw_list(ex[s].list, c->recs[s].type);
+    if (raw) raw_list(ex[s].list, c->recs[s].type, c->defl_mask);
     else strategy_list(ex[s].list, c->recs[s].type, c->strat_mask);
     if (ex[s].list.empty()) continue;
     todo.push_back((uint32_t)s);
@@ -3722,6 +3736,7 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
   p->mw_cap = mw_cap_for(todo.size());
   p->stopj_cur = nullptr;
   const atz_stats_t before = p->stats;
+  const double gnu_before = p->kt.gnu_ms;
   const SweepOpts so{c->o.recomp_tresh, c->o.sizediff_tresh, c->o.shortcut_len, c->o.mismatch_tol};
   const uint64_t budget = cap_bytes(ROUND_BUDGET_BYTES);
   RuleTally tally;
@@ -3742,7 +3757,7 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
       std::vector<std::pair<uint32_t, int>> need;
       for (size_t a = a0; a < a1; a++) {
         const uint32_t q = ex[act[a]].list[j];
-        if (raw ? ((q >> 16) & 0xff) > 0 : (q >> 24) == 1) need.push_back({act[a], (int)(q & 0xff)});
+        if (raw ? ((q >> 16) & 0xff) > 0 : (q >> 24) == 1) need.push_back({act[a], tab_memlevel(q)});
       }
       if (int r = private_chains(c, p, need)) return r;
       TrialBatch B;   // never saves, replays or stands for a duplicate
@@ -3751,7 +3766,7 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
         const int m = (int)(q & 0xff);
         const auto at = B.add(p, s, c->recs[s].infl_len, (int)((q >> 16) & 0xff), (int)((q >> 8) & 0xff), m, (q >> 24) & 3,
                               raw ? TM_RAW : 0, std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len)));
-        if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m];
+        if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][tab_memlevel(q)];
       }
       if (int r = B.reserve(p)) return r;
       std::vector<TrialRes> rr[3];
@@ -3810,6 +3825,9 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
   t.sweep_ms += ms_since(t0);
   if (timing_on()) std::fprintf(stderr, "atz: %s pass: %zu streams, %llu trials  %9.2f ms\n", raw ? "raw" : "strategy",
                                 todo.size(), (unsigned long long)tally.ntr, ms_since(t0));
+  if (timing_on() && raw && c->defl_mask)
+    std::fprintf(stderr, "atz: raw pass: k_trial_fast_gnu + k_trial_slow_gnu %9.3f ms of k_trial %9.3f ms\n",
+                 p->kt.gnu_ms - gnu_before, q.k_trial_ms - before.k_trial_ms);
   return 0;
 }
 static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
@@ -3821,14 +3839,21 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
 // use; --brute-window does not widen it), the default strategy, memLevels 8, 9, 7..1, and inside a
 // memLevel the levels in the order its container's hint suggests -- 90 entries, raw << 28 | c << 16 |
 // 15 << 8 | m.  The rule is strategy_pass's, on the body: a recorded one gets clevel = 1 << 6 | level.
-static void raw_list(std::vector<uint32_t>& l, int type) {
+// defl_mask bit 0 (atz_set_deflaters): GNU gzip's and Info-ZIP's deflater, levels 1-9 in the
+// hint's order, marked with memLevel 0, directly behind the memLevel-8 group (their parse is zlib's at
+// memLevel 8, so they share its tables) -- 99 entries.
+static void raw_list(std::vector<uint32_t>& l, int type, uint32_t defl_mask) {
   if (type < 24 || type > 26) return;
   static const int mo[9] = {8, 9, 7, 6, 5, 4, 3, 2, 1};
   static const int lo[3][10] = {{6, 9, 1, 5, 7, 8, 4, 3, 2, 0},    // no hint
                                 {1, 2, 3, 4, 5, 6, 7, 8, 9, 0},    // fast
                                 {9, 8, 7, 6, 5, 4, 3, 2, 1, 0}};   // max
-  for (int m : mo)
+  for (int m : mo) {
     for (int cl : lo[type - 24]) l.push_back((1u << 28) | pk(cl, 15, m));
+    if (m == 8 && (defl_mask & 1u))
+      for (int cl : lo[type - 24])
+        if (cl) l.push_back((1u << 28) | pk(cl, 15, 0));
+  }
 }
 static int raw_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
   return (c->cont_mask || c->probe_mask) ? ext_pass(c, d_file, ss, true) : 0;
@@ -3924,6 +3949,7 @@ static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<
 
 // version 2 (the strategy extension): some descriptor's clevel byte is strategy << 4 | level;
 // version 3 (the container extension): some descriptor's is raw << 6 | strategy << 4 | level
+// version 5 (the deflater extension): some raw descriptor's memLevel byte is 0, a GNU-family body
 static void atz_header(std::vector<uint8_t>& meta, uint64_t F, uint64_t nrec, uint8_t version = 1) {
   const uint8_t h[4] = {'A', 'T', 'Z', version};
   meta.insert(meta.end(), h, h + 4);
@@ -3937,12 +3963,13 @@ static int write_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::
   std::vector<Seg> segs;
   const size_t n = c->recs.size();
   uint64_t nrec = 0;
-  uint8_t version = 1;   // ATZ1 unless a recorded stream carries a strategy (2), is raw (3) or is stitched (4)
+  uint8_t version = 1;   // ATZ1 unless a recorded stream carries a strategy (2), is raw (3), is stitched (4) or is GNU's (5)
   size_t npieces = 0;
   for (size_t s = 0; s < n; s++) {
     nrec += ss[s].recomp;
     if (ss[s].recomp && (ss[s].c >> 4)) version = std::max<uint8_t>(version, (ss[s].c & 0x40) ? 3 : 2);
-    if (ss[s].recomp && c->recs[s].stitch != ~0ull) version = 4;
+    if (ss[s].recomp && c->recs[s].stitch != ~0ull) version = std::max<uint8_t>(version, 4);
+    if (ss[s].recomp && (ss[s].c & 0x40) && ss[s].m == 0) version = 5;   // a GNU-family body (memLevel byte 0)
     npieces += c->recs[s].stitch != ~0ull ? c->recs[s].pk : 1;
   }
   atz_header(meta, F, nrec, version);
@@ -4166,23 +4193,25 @@ static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std:
     // a batch: streams until the scratch estimate passes the budget (at least one)
     size_t s1 = s0;
     uint64_t bytes = 0;
+    // (bit 29: the GNU deflater family, memLevel field 0 -- TrialBatch::add's and sym_words' mark; its tables are
+    // memLevel 8's)
+    auto mlev = [&](size_t s) -> int { return (params[s] >> 29) & 1u ? 0 : (int)(params[s] & 0xff); };
     while (s1 < n && (s1 == s0 || bytes <= budget)) {
-      const int m = (int)(params[s1] & 0xff);
-      bytes += 9 * len[s1] + 4 * sym_words(p, 1, (uint32_t)m, len[s1]) + 4096;
+      bytes += 9 * len[s1] + 4 * sym_words(p, 1, (uint32_t)mlev(s1), len[s1]) + 4096;
       s1++;
     }
     c->chain_off.assign(n, {});
     std::vector<std::pair<uint32_t, int>> need;
     // (params carry a strategy in bits 24-25: Z_RLE and Z_HUFFMAN_ONLY read no bucket tables; bit 28: raw output)
     for (size_t s = s0; s < s1; s++)
-      if (((params[s] >> 16) & 0xff) > 0 && ((params[s] >> 24) & 3) < 2) need.push_back({(uint32_t)s, (int)(params[s] & 0xff)});
+      if (((params[s] >> 16) & 0xff) > 0 && ((params[s] >> 24) & 3) < 2) need.push_back({(uint32_t)s, mlev(s) ? mlev(s) : 8});
     if (int r = private_chains(c, p, need)) return r;
     TrialBatch B;
     for (size_t s = s0; s < s1; s++) {
-      const int m = (int)(params[s] & 0xff);
+      const int m = mlev(s);
       const auto at = B.add(p, (uint32_t)s, len[s], (int)((params[s] >> 16) & 0xff), (int)((params[s] >> 8) & 0xff), m,
                             (params[s] >> 24) & 3, (uint8_t)(TM_FULL | ((params[s] >> 28) & 1u ? TM_RAW : 0)), 0);
-      if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m];
+      if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m ? m : 8];
     }
     if (int r = B.reserve(p)) return r;
     SweepOpts so{0, 0, 0, 0};
@@ -4268,8 +4297,11 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
   // version 3: the container extension's (clevel = raw << 6 | strategy << 4 | level)
   // version 4: the stitch extension's (clevel = stitched << 7 | raw << 6 | strategy << 4 | level, never both
   // of bits 6 and 7; a stitched descriptor's piece list follows its payload: u32 k, k x u32 lengths)
-  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 4) return ATZ_E_FORMAT;   // main.cpp:1018-1021
-  const bool v2 = atz[3] == 2, v4 = atz[3] == 4, v3 = atz[3] == 3 || v4;
+  // version 5: the deflater extension's (version 4's, and a raw descriptor with the default strategy, level 1-9
+  // and memLevel byte 0 is a GNU-family body)
+  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 5) return ATZ_E_FORMAT;   // main.cpp:1018-1021
+  const bool v5 = atz[3] == 5;
+  const bool v2 = atz[3] == 2, v4 = atz[3] == 4 || v5, v3 = atz[3] == 3 || v4;
   if (rd8(atz + 4) != n) return ATZ_E_FORMAT;                              // main.cpp:1022-1025
   origlen = rd8(atz + 12);
   const uint64_t nstrms = rd8(atz + 20);
@@ -4319,6 +4351,10 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
     } else if (v2) {   // Z_HUFFMAN_ONLY and Z_RLE have no level 0
       if ((x.c & 15) > 9 || (x.c >> 4) > 3 || ((x.c >> 4) >= 2 && (x.c & 15) < 1)) return ATZ_E_REF_ABORT;
     } else if (x.c > 9) return ATZ_E_REF_ABORT;
+    if (v5 && x.m == 0) {   // GNU's: raw, not stitched (bit 7 was read above), default strategy, level 1-9, window 15
+      if ((x.c & 0xf0) != 0x40 || (x.c & 15) < 1 || x.w != 15 || x.k) return ATZ_E_REF_ABORT;
+      continue;
+    }
     if (x.w < 8 || x.w > 15 || x.m < 1 || x.m > 9) return ATZ_E_REF_ABORT;
   }
   // streams in file order, inside the original (the writer emits them so; a crafted file with
@@ -4390,6 +4426,7 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
       const int w = d[j].w == 8 ? 9 : d[j].w;
       params[j] = ((uint32_t)((d[j].c >> 6) & 1) << 28) | ((uint32_t)((d[j].c >> 4) & 3) << 24) |
                   ((uint32_t)(d[j].c & 15) << 16) | ((uint32_t)w << 8) | d[j].m;
+      if (d[j].m == 0) params[j] |= 1u << 29;   // a GNU-family body (parse_atz: version 5 only)
     }
     if (!segs.empty())
       if (int r = gather_segments(c, d_atz, meta, segs, slab.as<uint8_t>())) return r;
@@ -4957,7 +4994,7 @@ int atz_deflate(atz_ctx_t* c, const uint8_t* in, uint64_t in_len, int clevel, in
   });
 }
 
-// ex: params carry zlib's strategy in bits 24-27 and the raw flag in bit 28 (atz_deflate_batch_ex); else
+// ex: params carry zlib's strategy in bits 24-27, the raw flag in bit 28 and the GNU deflater in bit 29 (atz_deflate_batch_ex); else
 // bits 16-31 are the level
 static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
                              const uint32_t* params, uint64_t n, uint8_t* out, const uint64_t* out_offs,
@@ -4970,13 +5007,18 @@ static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, con
     for (uint64_t k = 0; k < n; k++) {
       if (offs[k] + lens[k] > len) return ATZ_E_ARG;
       const uint32_t raw = ex ? (params[k] >> 28) & 1u : 0u;   // no zlib header, no Adler-32 trailer
-      const int sg = ex ? (int)((params[k] >> 24) & ~16u) : 0;
+      const uint32_t gnu = ex ? (params[k] >> 29) & 1u : 0u;   // the GNU deflater family: raw, window 15, level 1-9 only
+      const int sg = ex ? (int)((params[k] >> 24) & ~(16u | 32u)) : 0;
       int cl = (int)(ex ? (params[k] >> 16) & 0xff : params[k] >> 16), w = (int)((params[k] >> 8) & 0xff), m = (int)(params[k] & 0xff);
-      if (cl < 0 || cl > 9 || w < 8 || w > 15 || m < 1 || m > 9) return ATZ_E_ARG;
+      if (gnu) {   // (the memLevel field is ignored)
+        if (!raw || sg != 0 || w != 15 || cl < 1 || cl > 9) return ATZ_E_ARG;
+        m = 0;
+      } else if (m < 1 || m > 9) return ATZ_E_ARG;
+      if (cl < 0 || cl > 9 || w < 8 || w > 15) return ATZ_E_ARG;
       if (sg > 3 || (sg >= 2 && cl < 1)) return ATZ_E_ARG;   // Z_FIXED is not supported; Z_RLE / Z_HUFFMAN_ONLY have no level 0
       if (w == 8) w = 9;
       ins[k] = {buf + offs[k], lens[k]};
-      ps[k] = (raw << 28) | ((uint32_t)sg << 24) | ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
+      ps[k] = (gnu << 29) | (raw << 28) | ((uint32_t)sg << 24) | ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
     }
     std::vector<std::vector<uint8_t>> outs;
     if (int r = deflate_many(c, ins, ps, outs)) return r;
@@ -5060,6 +5102,12 @@ int atz_set_probe(atz_ctx_t* c, uint32_t mask) {
   return ATZ_OK;
 }
 
+int atz_set_deflaters(atz_ctx_t* c, uint32_t mask) {
+  if (!c || (mask & ~1u)) return ATZ_E_ARG;   // bit 0: GNU gzip's and Info-ZIP's deflater, for raw records
+  c->defl_mask = mask;
+  return ATZ_OK;
+}
+
 int atz_probe_positions(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint64_t** out, uint64_t* n) {
   return guarded([&]() -> int {
     (void)hipGetLastError();
@@ -5116,7 +5164,7 @@ int atz_shard_scan(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, u
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !blob || !blob_len || world < 1 || rank < 0 || rank >= world) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
+    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
     dev_mark_call();   // (the peak runs on through atz_shard_sweep, whose stats report it)
     std::vector<uint64_t> b;
     if (int r = shard_scan_impl(c, d_file, h_file, len, rank, world, b)) { c->shard.stage = 0; return r; }
@@ -5134,7 +5182,7 @@ int atz_shard_sweep(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, 
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !piece_len || !recomp_flags || !n_flags || !n_recomp) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask) return ATZ_E_ARG;
+    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask) return ATZ_E_ARG;
     std::vector<uint8_t> f;
     if (int r = shard_sweep_impl(c, d_file, h_file, len, blobs, blob_lens, world, f, n_recomp)) {
       c->shard.stage = 0;

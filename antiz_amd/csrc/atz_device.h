@@ -62,6 +62,7 @@ enum : uint32_t {
   TH_STRAT = 3,   // mask: zlib's strategy number (0 default, 1 Z_FILTERED, 2 Z_HUFFMAN_ONLY, 3 Z_RLE)
   TH_WAITS = 4,   // waits for a saver of this round (launched in the round's second set)
   TH_DUP = 8,     // a duplicate of an earlier trial's result: not launched
+  TH_GNU = 16,    // the GNU deflater family (k_trial_{fast,slow}_gnu): memlevel is 8, the symbol buffer 32 768 + 64
 };
 struct Trial {
   uint32_t stream;   // index into the stream table

@@ -1983,7 +1983,11 @@ static constexpr uint32_t TR_DECIDED = 0xfffffffeu;   // parser-side: a flusher 
 // KIND: 0 deflate_stored, 1 deflate_fast, 2 deflate_slow, 3 deflate_rle, 4 deflate_huff (the last two take
 // no chains and no match table).  STRAT: 1 = deflate_slow under Z_FILTERED (Trial::host carries zlib's
 // strategy number, which no kernel reads: the host picks the instantiation by it).
-template <int KIND, typename SH, int STRAT = 0>
+// FAM: the deflater family (Trial::host & TH_GNU, likewise the host's pick).  0 zlib.  1 GNU gzip's and Info-ZIP's
+// deflate.c / trees.c: zlib's parse at memLevel 8, zlib's trees and emission, but ct_tally's
+// blocks -- a buffer of 32 768 symbols, and for levels above 2 a check at every 4 096th symbol of the block
+// that ends it early when matches are few and the block already halves its input (due / flush_here).
+template <int KIND, typename SH, int STRAT = 0, int FAM = 0>
 struct TrialRun {
   static constexpr bool MW = HasMW<SH>::value;
   static constexpr bool TAB = KIND == 1 || KIND == 2;   // the parse reads chains and a match table
@@ -2016,6 +2020,7 @@ struct TrialRun {
   uint64_t cstart = 0;
   uint32_t rtstart = 0;
   uint32_t hazard = 0;
+  uint32_t gmat = 0;             // FAM 1: matches tallied into the block (ct_tally's last_dist), wave-uniform
   // Symbols and block statistics are tallied straight into HBM (syms) and LDS (lfreq / dfreq).
   uint32_t state = ~0u;
   uint64_t fallbacks = 0, cyc_fb = 0;
@@ -2038,7 +2043,7 @@ struct TrialRun {
         sidx(!TAB ? nullptr : A_.chains + tr.chain_off), bpos(!TAB ? nullptr : sidx + npad),
         full_needed(tr.mode & TM_FULL), lt(lane_ ? (~0ull >> (64 - lane_)) : 0ull) {
     z.level = tr.clevel; z.kind = KIND;
-    z.wsize = 1u << tr.window; z.maxdist = z.wsize - LOOKMIN; z.lbs = 1u << (tr.memlevel + 6);
+    z.wsize = 1u << tr.window; z.maxdist = z.wsize - LOOKMIN; z.lbs = FAM == 1 ? 32768u : 1u << (tr.memlevel + 6);
     z.good = c_cfg[z.level][0]; z.lazy = c_cfg[z.level][1]; z.nice = c_cfg[z.level][2]; z.chain = c_cfg[z.level][3];
     z.n = sd.infl_len; z.p = 0; z.lookahead = 0; z.S = 0; z.block_start = 0;
     z.match_start = 0; z.prev_match = 0; z.match_length = 2; z.prev_length = 2; z.match_available = 0;
@@ -2143,9 +2148,11 @@ struct TrialRun {
       return true;
   }
   __device__ __forceinline__ void FLUSH(int last) {
-      hazard |= uni(flush_block(s, *(LDS TreeScratch*)shm.ring, b, (const GLOBAL uint32_t*)syms + ((saving || replay) ? sbase : 0u),
+      const uint32_t hz = uni(flush_block(s, *(LDS TreeScratch*)shm.ring, b, (const GLOBAL uint32_t*)syms + ((saving || replay) ? sbase : 0u),
                                 (const GLOBAL uint8_t*)in, (int64_t)z.block_start, z.p, z.S, z.last_lit, z.level, z.lbs, last,
                                 A.o, tr.best_ident, full_needed, lane));
+      hazard |= FAM == 1 ? 0u : hz;   // (the overlay is zlib 1.2.8's: GNU's symbol buffers are arrays of their own)
+      if (FAM == 1) gmat = 0;
       sbase += z.last_lit;
       z.last_lit = 0;
       z.block_start = z.p;
@@ -2164,6 +2171,35 @@ struct TrialRun {
         FLUSH(0);
         const uint32_t e = uni(early_exit(b, A.o, tr.best_ident, full_needed));
         return e == ~0u && spec_stopped(s) ? TR_SKIPPED : e;
+      }
+  }
+  // The block's end, asked after each tallied run of symbols.  zlib: the buffer is full.  FAM 1 (ct_tally in
+  // GNU's trees.c): for levels above 2 also when the block's symbol count is a multiple of 4 096 and
+  //   last_dist < last_lit / 2  and  (last_lit * 8 + sum_c dfreq[c] * (5 + extra_dbits[c])) >> 3  <  (strstart - block_start) / 2
+  // with strstart at the tally: the symbol's start for deflate_fast, one past it for the lazy parse.  room():
+  // symbols a run may tally before the next such point; due(): the count stands at one; flush_here(strstart):
+  // the block ends there (the sum over the 30 distance codes is one wave reduction, taken at those points only).
+  __device__ __forceinline__ uint32_t room() const {
+      uint32_t r = z.lbs - 1u - z.last_lit;
+      if (FAM == 1 && z.level > 2) {
+        const uint32_t r2 = 4096u - (z.last_lit & 4095u);
+        r = r2 < r ? r2 : r;
+      }
+      return r;
+  }
+  __device__ __forceinline__ bool due() const {
+      return z.last_lit == z.lbs - 1u || (FAM == 1 && z.level > 2 && (z.last_lit & 4095u) == 0);
+  }
+  __device__ __forceinline__ bool flush_here(uint32_t strstart) const {
+      if constexpr (FAM == 1) {
+        if (z.last_lit == z.lbs - 1u) return true;
+        const uint32_t dc = (uint32_t)lane < (uint32_t)NDC ? (uint32_t)lane : 0u;
+        const uint32_t fr = (s.f.dfreq2[dc >> 1] >> (16u * (dc & 1u))) & 0xffffu;
+        const uint32_t bits = (uint32_t)lane < (uint32_t)NDC ? fr * (5u + c_xdb[dc]) : 0u;
+        const uint32_t out = (z.last_lit * 8u + uni((uint32_t)wsum64(bits))) >> 3;
+        return gmat < z.last_lit / 2u && out < (uni(strstart) - z.block_start) / 2u;
+      } else {
+        return true;
       }
   }
 
@@ -2489,8 +2525,8 @@ struct TrialRun {
       }
     }
   };
-  // one symbol, tallied by the scalar unit; returns true when the block is full
-  auto tally1 = [&](uint32_t v) -> bool {
+  // one symbol (starting at position at), tallied by the scalar unit; returns true when the block ends
+  auto tally1 = [&](uint32_t v, uint32_t at) -> bool {
     if (lane == 0) {
       syms[(saving || MW ? sbase : 0u) + z.last_lit] = v;
       if (v >> 8) {
@@ -2502,7 +2538,8 @@ struct TrialRun {
     }
     z.last_lit++;
     z.nsym++;
-    return z.last_lit == z.lbs - 1u;
+    if (FAM == 1) gmat += (v >> 8) ? 1u : 0u;
+    return FAM == 1 ? due() && flush_here(at) : z.last_lit == z.lbs - 1u;
   };
   uint32_t q = 0, Sb = 0;
   bool need = false;
@@ -2593,8 +2630,9 @@ struct TrialRun {
         z.nsym += T;
         uint32_t base = 0;
         while (base < T) {
-          const uint32_t room = z.lbs - 1u - z.last_lit;
+          const uint32_t room = this->room();
           const uint32_t seg_end = T - base < room ? T : base + room;
+          if (FAM == 1) gmat += (uint32_t)__popcll(__ballot(mine && o >= base && o < seg_end && wt == 2));
           if (mine && o >= base && o < seg_end) {
             uint32_t v;
             if (wt == 2) {
@@ -2608,15 +2646,17 @@ struct TrialRun {
             syms[(saving || MW ? sbase : 0u) + z.last_lit + (o - base)] = v;
           }
           z.last_lit += seg_end - base;
-          if (z.last_lit == z.lbs - 1u) {   // flush after the node tallied last: strstart past its step
+          if (due()) {   // flush after the node tallied last: strstart past its step
             const uint64_t om = __ballot(mine && o == seg_end - 1u);
             const int ol = (int)__builtin_ctzll(om);
             const uint32_t fx = (uint32_t)__builtin_amdgcn_readlane((int)x, ol);
             const uint32_t fl = (uint32_t)__builtin_amdgcn_readlane((int)L, ol);
-            z.p = fx + (fl ? fl : 1u);
-            z.S = S_iter(Sb, fx);
-            state = FLUSH0();
-            if (state != ~0u) break;
+            if (flush_here(fx)) {
+              z.p = fx + (fl ? fl : 1u);
+              z.S = S_iter(Sb, fx);
+              state = FLUSH0();
+              if (state != ~0u) break;
+            }
           }
           base = seg_end;
         }
@@ -2656,7 +2696,7 @@ struct TrialRun {
       fallbacks += 1ull << 32;   // diagnostics: walks that changed the path (high half)
       const uint32_t step = ml >= 3 ? ml : 1u;
       span_set(f, f + step, [&](uint32_t p, uint32_t& y, uint32_t& Ly) { y = f; Ly = ml >= 3 ? ml : 0u; });
-      const bool full = tally1(ml >= 3 ? (((f - ms) << 8) | (ml - 3u)) : (uint32_t)in[f]);
+      const bool full = tally1(ml >= 3 ? (((f - ms) << 8) | (ml - 3u)) : (uint32_t)in[f], f);
       if (full) {
         z.p = f + step;
         z.S = Sf;
@@ -2777,8 +2817,10 @@ struct TrialRun {
     z.nsym += T;
     uint32_t base = 0;
     while (base < T) {
-      const uint32_t room = z.lbs - 1u - z.last_lit;
+      const uint32_t room = this->room();
       const uint32_t seg_end = T - base < room ? T : base + room;
+      if (FAM == 1)   // a node's match is its last symbol
+        gmat += (uint32_t)__popcll(__ballot(cnt && wt == 2 && o + cnt - 1u >= base && o + cnt - 1u < seg_end));
       const uint32_t klo = o > base ? 0u : base - o;
       const uint32_t khi = o + cnt < seg_end ? cnt : (seg_end > o ? seg_end - o : 0u);
       for (uint32_t k = klo; k < khi; k++) {
@@ -2797,7 +2839,7 @@ struct TrialRun {
         syms[(saving || MW ? sbase : 0u) + z.last_lit + (o + k - base)] = v;
       }
       z.last_lit += seg_end - base;
-      if (z.last_lit == z.lbs - 1u) {
+      if (due()) {
         // flush after symbol seg_end - 1: strstart = its iteration + 1 for a literal (the
         // literal of y is tallied at iteration y + 1), match end for a match (tallied at m + 1)
         const uint32_t g = seg_end - 1u;
@@ -2811,10 +2853,12 @@ struct TrialRun {
         }
         const uint64_t om = __ballot(own);
         const int ol = (int)__builtin_ctzll(om);
-        z.p = (uint32_t)__builtin_amdgcn_readlane((int)fp, ol);
-        z.S = S_iter(Sb, (uint32_t)__builtin_amdgcn_readlane((int)fit, ol));
-        state = FLUSH0();
-        if (state != ~0u) break;
+        if (flush_here((uint32_t)__builtin_amdgcn_readlane((int)fit, ol))) {   // (fit: strstart at the symbol's tally)
+          z.p = (uint32_t)__builtin_amdgcn_readlane((int)fp, ol);
+          z.S = S_iter(Sb, (uint32_t)__builtin_amdgcn_readlane((int)fit, ol));
+          state = FLUSH0();
+          if (state != ~0u) break;
+        }
       }
       base = seg_end;
     }
@@ -3119,7 +3163,7 @@ struct TrialRun {
   }
 };
 
-template <int KIND, typename SH, int STRAT = 0>
+template <int KIND, typename SH, int STRAT = 0, int FAM = 0>
 __device__ void trial_body(const SweepArgs& A, SH& shm, int lane) {
   if constexpr (!HasMW<SH>::value) {
     // a single-wave trial whose stream an earlier trial of the round has stopped ends before any set-up
@@ -3136,7 +3180,7 @@ __device__ void trial_body(const SweepArgs& A, SH& shm, int lane) {
       return;
     }
   }
-  TrialRun<KIND, SH, STRAT> run(A, shm, lane);
+  TrialRun<KIND, SH, STRAT, FAM> run(A, shm, lane);
   run.run();
 }
 
@@ -3186,6 +3230,17 @@ __global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_rle(SweepArgs A)
 __global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_huff(SweepArgs A) {
   __shared__ TrialSharedSlow shm;
   trial_body<4>(A, shm, threadIdx.x);
+}
+// GNU-family trials (Trial::host & TH_GNU; opt-in): deflate_fast and the lazy parse on the
+// stream's memLevel-8 buckets and match tables, with ct_tally's blocks.  Single-wave, TM_RAW, never a saver,
+// a replay or a duplicate (the host's side: ext_pass, deflate_dev).
+__global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_fast_gnu(SweepArgs A) {
+  __shared__ TrialSharedFast<BITMAP_BITS> shm;
+  trial_body<1, TrialSharedFast<BITMAP_BITS>, 0, 1>(A, shm, threadIdx.x);
+}
+__global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_slow_gnu(SweepArgs A) {
+  __shared__ TrialSharedSlow shm;
+  trial_body<2, TrialSharedSlow, 0, 1>(A, shm, threadIdx.x);
 }
 
 }  // namespace atz

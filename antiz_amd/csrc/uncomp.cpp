@@ -399,8 +399,8 @@ int main(int argc, char* argv[]) {
     }
     // ("ATZ\2": a file of the strategy extension, ATZ_STRATEGIES below; "ATZ\3": of the container extension,
     // ATZ_CONTAINERS; same layout; "ATZ\4": of the stitch extension, ATZ_STITCH, whose stitched descriptors carry a
-    // piece list)
-    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 4) {
+    // piece list; "ATZ\5": of the deflater extension, ATZ_DEFLATERS, version 4's layout)
+    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 5) {
       std::cout << "Invalid file: ATZ1 header not found" << std::endl;
       return -2;
     }
@@ -498,7 +498,23 @@ int main(int argc, char* argv[]) {
       }
     }
   }
+  // ATZ_DEFLATERS=gnu (not a reference flag): the raw records' walk also tries the deflater of GNU gzip and
+  // Info-ZIP's zip (atz_set_deflaters)
+  uint32_t deflaters = 0;
+  if (const char* e = std::getenv("ATZ_DEFLATERS")) {
+    std::stringstream words(e);
+    std::string w;
+    while (std::getline(words, w, ',')) {
+      if (w.empty()) continue;
+      if (w == "gnu") deflaters |= 1u << 0;
+      else {
+        std::cerr << "Error Encountered: " << "ATZ_DEFLATERS: unknown deflater " << w << std::endl;
+        return done(1);
+      }
+    }
+  }
   if (open_ctx()) return done(255);
+  if (deflaters && atz_set_deflaters(ctx, deflaters) != 0) return done(255);
   if (strategies && atz_set_strategies(ctx, strategies) != 0) return done(255);
   if (containers && atz_set_containers(ctx, containers) != 0) return done(255);
   if (stitch && atz_set_stitch(ctx, stitch) != 0) return done(255);

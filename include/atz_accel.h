@@ -17,10 +17,11 @@
  *   atz_deflate     one deflateInit2/deflate(Z_FINISH)/deflateEnd              main.cpp:976-1003
  *   atz_shard_*     the precompress of one file split over several GPUs (new: the reference is
  *                   single-threaded)
- * Four opt-in extensions, each off by default and leaving every output as the reference's while off:
+ * Five opt-in extensions, each off by default and leaving every output as the reference's while off:
  *   atz_set_strategies  zlib strategy trials ("ATZ\2"), atz_set_containers  raw deflate in ZIP / gzip ("ATZ\3"),
  *   atz_set_stitch      zlib streams split over PNG IDAT chunks ("ATZ\4"),
- *   atz_set_probe       raw deflate streams that nothing announces ("ATZ\3")
+ *   atz_set_probe       raw deflate streams that nothing announces ("ATZ\3"),
+ *   atz_set_deflaters   raw bodies written by GNU gzip's and Info-ZIP's deflater, not zlib's ("ATZ\5")
  */
 #ifndef ATZ_ACCEL_H
 #define ATZ_ACCEL_H
@@ -234,6 +235,20 @@ int atz_set_probe(atz_ctx_t *ctx, uint32_t mask);
 /* The probe kernel's list for a host buffer (parity/debug): *out (atz_free) receives the *n surviving
  * positions, ascending, as plain positions. */
 int atz_probe_positions(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint64_t **out, uint64_t *n);
+
+/* Opt-in deflater families (an extension: the raw walk only knows zlib 1.2.8's deflater).  mask bit 0: "gnu",
+ * the deflater of GNU gzip and of Info-ZIP's zip (one family: zlib's parse at memLevel 8 and zlib's trees, but
+ * blocks of up to 32 767 symbols that, for levels above 2, may end at every 4 096th symbol); 0, the default, is
+ * off and leaves every output as what a context without this mask writes.  The mask acts on raw records only
+ * (atz_cand_t.type 24-26, from atz_set_containers and atz_set_probe; alone it changes nothing): their walk
+ * gets nine more candidates, levels 1-9 in the hint's order, directly behind the memLevel-8 group (positions
+ * 10-18 of 99).  A body recorded so reports clevel = 1<<6 | level, window 15 and memLevel 0, and a file that
+ * holds one is written with the magic "ATZ\5" (version 4's layout; memLevel byte 0 only on such a descriptor),
+ * else the file is what a context without this mask writes.  atz_reconstruct* read all five.  In
+ * atz_deflate_batch_ex, bit 29 of a params word asks for this deflater: only with bit 28, window 15, strategy
+ * 0 and level 1-9 (else ATZ_E_ARG); the memLevel field is ignored.  The atz_shard_* calls return ATZ_E_ARG on
+ * a context with a mask. */
+int atz_set_deflaters(atz_ctx_t *ctx, uint32_t mask);
 
 /* Batch of independent one-shot inflates of the given ranges of a host buffer (parity/debug):
  * status[i] in {0 end, 1 error, 2 need input}, consumed[i] = zlib total_in, produced[i] = total_out. */
