@@ -56,7 +56,8 @@ EXPORTS = ["atz_open", "atz_close", "atz_strerror", "atz_free", "atz_default_opt
            "atz_inflate_batch", "atz_deflate_bound", "atz_shard_scan", "atz_shard_sweep", "atz_shard_piece",
            "atz_shard_assemble", "atz_reconstruct_device", "atz_deflate_batch_ex", "atz_set_strategies",
            "atz_set_containers", "atz_container_anchors", "atz_set_stitch", "atz_stitch_anchors",
-           "atz_stitch_pieces", "atz_set_probe", "atz_probe_positions", "atz_set_deflaters"]
+           "atz_stitch_pieces", "atz_set_probe", "atz_probe_positions", "atz_set_deflaters",
+           "atz_set_segments", "atz_flush_markers", "atz_inflate_segments"]
 
 # zlib's strategy numbers (Z_FIXED, 4, is not supported); a strategy mask has bit k set for strategy k
 STRATEGIES = {"filtered": 1, "huffman": 2, "rle": 3}
@@ -135,6 +136,22 @@ def deflater_mask(names):
         if w not in DEFLATERS:
             raise ValueError("unknown deflater %r (known: %s)" % (w, ", ".join(sorted(DEFLATERS))))
         mask |= 1 << DEFLATERS[w]
+    return mask
+
+
+# what a segments mask makes the scan split streams at: bit number of each
+SEGMENTS = {"flush": 0}
+
+
+def segments_mask(names):
+    """("flush",) or a comma-separated string -> atz_set_segments mask; ValueError on an unknown word."""
+    if isinstance(names, str):
+        names = [w for w in names.split(",") if w]
+    mask = 0
+    for w in names:
+        if w not in SEGMENTS:
+            raise ValueError("unknown segment kind %r (known: %s)" % (w, ", ".join(sorted(SEGMENTS))))
+        mask |= 1 << SEGMENTS[w]
     return mask
 
 
@@ -217,6 +234,10 @@ def lib():
         L.atz_set_probe.argtypes = [C.c_void_p, C.c_uint32]
         L.atz_probe_positions.argtypes = [C.c_void_p, C.c_char_p, u64, C.POINTER(C.POINTER(u64)), C.POINTER(u64)]
         L.atz_set_deflaters.argtypes = [C.c_void_p, C.c_uint32]
+        L.atz_set_segments.argtypes = [C.c_void_p, C.c_uint32]
+        L.atz_flush_markers.argtypes = L.atz_probe_positions.argtypes
+        L.atz_inflate_segments.argtypes = [C.c_void_p, C.c_char_p, u64, C.POINTER(u64), C.POINTER(u64), u64,
+                                           C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint8)]
         L.atz_deflate_bound.restype = u64
         L.atz_deflate_bound.argtypes = [u64, C.c_int, C.c_int]
         L.atz_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, u64, C.c_int, C.c_int, C.POINTER(u8p),
@@ -243,7 +264,7 @@ class Context:
 
     def __init__(self, recomp_tresh=128, sizediff_tresh=128, shortcut_len=512, mismatch_tol=2,
                  chunksize=524288, brute_window=False, device=-1, strategies=None, containers=None, stitch=None,
-                 probe=None, deflaters=None):
+                 probe=None, deflaters=None, segments=None):
         """strategies: names of zlib strategies ("filtered", "rle", "huffman") to try on the streams the
         reference walk leaves unrecorded (an extension, off by default; None reads ATZ_STRATEGIES, a
         comma-separated list, as the CLI does).
@@ -255,7 +276,9 @@ class Context:
         container announces (an extension, off by default; None reads ATZ_PROBE, a comma-separated list, as the
         CLI does).
         deflaters: "gnu": the raw records' walk (containers, probe) also tries the deflater of GNU gzip and Info-ZIP's
-        zip (an extension, off by default; None reads ATZ_DEFLATERS, a comma-separated list, as the CLI does)."""
+        zip (an extension, off by default; None reads ATZ_DEFLATERS, a comma-separated list, as the CLI does).
+        segments: "flush": a stream cut by full-flush points (Z_FULL_FLUSH, pigz -i) is recorded as one raw record per
+        segment (an extension, off by default; None reads ATZ_SEGMENTS, a comma-separated list, as the CLI does)."""
         L = lib()
         self.o = Opts(recomp_tresh, sizediff_tresh, shortcut_len, mismatch_tol, chunksize, int(brute_window), device)
         if strategies is None:
@@ -273,6 +296,9 @@ class Context:
         if deflaters is None:
             deflaters = os.environ.get("ATZ_DEFLATERS", "")
         dmask = deflater_mask(deflaters)
+        if segments is None:
+            segments = os.environ.get("ATZ_SEGMENTS", "")
+        gmask = segments_mask(segments)
         self.h = C.c_void_p()
         _check(L.atz_open(C.byref(self.h), C.byref(self.o)))
         if mask:
@@ -285,6 +311,8 @@ class Context:
             _check(L.atz_set_probe(self.h, pmask))
         if dmask:
             _check(L.atz_set_deflaters(self.h, dmask))
+        if gmask:
+            _check(L.atz_set_segments(self.h, gmask))
 
     def close(self):
         if self.h:
@@ -424,6 +452,16 @@ class Context:
         L.atz_free(p)
         return out
 
+    def flush_markers(self, data):
+        """The marker kernel's list for `data` (parity/debug): every q with data[q:q+4] == 00 00 FF FF, ascending."""
+        L = lib()
+        p = C.POINTER(u64)()
+        n = u64(0)
+        _check(L.atz_flush_markers(self.h, data, len(data), C.byref(p), C.byref(n)))
+        out = [p[i] for i in range(n.value)]
+        L.atz_free(p)
+        return out
+
     def stitch_pieces(self, record):
         """[(file offset, length)] of the pieces of stitched record `record` of the last scan ([]: not stitched)."""
         L = lib()
@@ -435,11 +473,11 @@ class Context:
         L.atz_free(pl)
         return out
 
-    def deflate(self, data, clevel, window, memlevel, strategy=0, raw=False, deflater=None):
+    def deflate(self, data, clevel, window, memlevel, strategy=0, raw=False, deflater=None, flush=False):
         """deflater: None zlib 1.2.8's; "gnu" GNU gzip's and Info-ZIP's (raw, window 15, strategy 0, level 1-9 only;
-        memlevel is ignored)."""
-        if strategy or raw or deflater:
-            return self.deflate_batch(data, [(0, len(data), clevel, window, memlevel, strategy, raw, deflater)])[0]
+        memlevel is ignored).  flush: the body ends as deflate(Z_FULL_FLUSH) ends it (raw, zlib's, strategy 0 only)."""
+        if strategy or raw or deflater or flush:
+            return self.deflate_batch(data, [(0, len(data), clevel, window, memlevel, strategy, raw, deflater, flush)])[0]
         L = lib()
         cap = L.atz_deflate_bound(len(data), 10, 1) + 1024
         out = C.create_string_buffer(cap)
@@ -448,14 +486,16 @@ class Context:
         return out.raw[:n.value]
 
     def deflate_batch(self, buf, items):
-        """items: list of (offset, length, clevel, window, memlevel[, strategy[, raw[, deflater]]]) over `buf`; returns
-        list of bytes.  raw: the deflate body alone (no zlib header, no Adler-32 trailer).  deflater: see deflate()."""
+        """items: list of (offset, length, clevel, window, memlevel[, strategy[, raw[, deflater[, flush]]]]) over `buf`;
+        returns list of bytes.  raw: the deflate body alone (no zlib header, no Adler-32 trailer).  deflater, flush: see
+        deflate()."""
         L = lib()
         k = len(items)
         offs = (u64 * max(k, 1))(*[it[0] for it in items])
         lens = (u64 * max(k, 1))(*[it[1] for it in items])
-        ex = any(any(it[5:8]) for it in items)
-        prm = (C.c_uint32 * max(k, 1))(*[((deflater_mask((it[7],)) << 29) if len(it) > 7 and it[7] else 0) |
+        ex = any(any(it[5:9]) for it in items)
+        prm = (C.c_uint32 * max(k, 1))(*[((1 << 30) if len(it) > 8 and it[8] else 0) |
+                                         ((deflater_mask((it[7],)) << 29) if len(it) > 7 and it[7] else 0) |
                                          ((1 << 28) if len(it) > 6 and it[6] else 0) |
                                          ((it[5] << 24) if len(it) > 5 else 0) | (it[2] << 16) | (it[3] << 8) | it[4]
                                          for it in items])
@@ -483,3 +523,17 @@ class Context:
         pr = (u64 * max(k, 1))()
         _check(L.atz_inflate_batch(self.h, buf, len(buf), offs, lens, k, st, co, pr))
         return [(st[i], co[i], pr[i]) for i in range(k)]
+
+    def inflate_segments(self, buf, ranges):
+        """inflate_batch on raw deflate bodies with the segment decoder, which also ends (status 0) at a flush
+        marker: [(status, consumed, produced, at_marker)]."""
+        L = lib()
+        k = len(ranges)
+        offs = (u64 * max(k, 1))(*[a for a, _ in ranges])
+        lens = (u64 * max(k, 1))(*[b for _, b in ranges])
+        st = (C.c_uint32 * max(k, 1))()
+        co = (u64 * max(k, 1))()
+        pr = (u64 * max(k, 1))()
+        am = (C.c_uint8 * max(k, 1))()
+        _check(L.atz_inflate_segments(self.h, buf, len(buf), offs, lens, k, st, co, pr, am))
+        return [(st[i], co[i], pr[i], bool(am[i])) for i in range(k)]

@@ -660,6 +660,11 @@ struct ProbeList {   // the probe extension's survivors
   double kernel_ms = 0;        // k_probe_ordered, both passes
 };
 
+struct MarkerList {   // the segment extension's flush markers
+  std::vector<uint64_t> pos;   // every q with bytes q..q+3 = 00 00 FF FF, ascending
+  double kernel_ms = 0;        // k_marker_ordered, both passes
+};
+
 struct atz_ctx {
   KTimer kt;
   atz_opts_t o{};
@@ -692,6 +697,9 @@ struct atz_ctx {
   // opt-in probe (atz_set_probe): bit 0 raw deflate streams whose first block is dynamic, which no header or
   // container announces -- records of type 24 (raw, no hint), walked by raw_pass; 0: off
   uint32_t probe_mask = 0;
+  // opt-in segments (atz_set_segments): bit 0 streams cut by full-flush points become one raw record per
+  // segment (seg_merge), the flush-terminated ones with Rec::flags bit 7; 0: off
+  uint32_t seg_mask = 0;
   // opt-in deflater families for the raw walk (atz_set_deflaters): bit 0 GNU gzip's and Info-ZIP's; 0: zlib's only
   uint32_t defl_mask = 0;
   DBuf d_stitch;
@@ -751,6 +759,7 @@ struct atz_ctx {
   // the probe extension's list for the current scan (kept here, not in precompress_dev's frame, whose
   // layout the sweep's threads share: with the mask off the call's stack is exactly what it was)
   ProbeList probe;
+  MarkerList marks;   // the segment extension's, likewise
 };
 
 // kind: 0 trial, 1 inflate, 2 chains, 3 other, 4 match tables, 5 GNU-family trial (counted as a trial too)
@@ -863,9 +872,10 @@ static int timing_level() {   // ATZ_TIMING=1: phase timings, 2: + per-round swe
 }
 static bool timing_on() { return timing_level() >= 1; }
 
+static constexpr int INF_SEG = 2;   // run_inflate_jobs' raw argument: k_inflate's SEG variant
 static int run_inflate_jobs(atz_ctx* c, const uint8_t* d_in, uint8_t* d_out, const std::vector<InfJob>& jobs,
                             std::vector<InfRes>& res, uint64_t arena_cap = 0, bool full_ring = false,
-                            bool arena_reset = true, bool raw = false) {
+                            bool arena_reset = true, int raw = 0) {
   res.resize(jobs.size());
   if (jobs.empty()) return 0;
   auto ti0 = std::chrono::steady_clock::now();
@@ -882,9 +892,12 @@ static int run_inflate_jobs(atz_ctx* c, const uint8_t* d_in, uint8_t* d_out, con
   bool small = !full_ring;
   for (const InfJob& jb : jobs) small = small && jb.out_off != NO_OUT;
   kbeg(c, 1);
-  // raw: deflate bodies without the zlib wrapper (the container extension's candidates and records)
-  auto kern = small ? (raw ? k_inflate<INF_RING_SMALL, true> : k_inflate<INF_RING_SMALL>)
-                    : (raw ? k_inflate<INF_RING_FULL, true> : k_inflate<INF_RING_FULL>);
+  // raw 1: deflate bodies without the zlib wrapper (the container extension's candidates and records);
+  // raw 2 (INF_SEG): such bodies that also end at a flush marker (the segment extension)
+  auto kern = small ? (raw == INF_SEG ? k_inflate<INF_RING_SMALL, true, true>
+                       : raw          ? k_inflate<INF_RING_SMALL, true> : k_inflate<INF_RING_SMALL>)
+                    : (raw == INF_SEG ? k_inflate<INF_RING_FULL, true, true>
+                       : raw          ? k_inflate<INF_RING_FULL, true> : k_inflate<INF_RING_FULL>);
   hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, c->st, d_in, d_out, c->d_jobs.as<InfJob>(), c->d_res.as<InfRes>(), n,
                      c->d_arena.as<uint8_t>(), c->d_arena_used.as<unsigned long long>(), arena_cap);
   kend(c);
@@ -1741,6 +1754,104 @@ static int probe_merge(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint64_t a
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Opt-in segments (atz_set_segments).  deflate(Z_FULL_FLUSH) ends a segment with an empty
+// stored block (its byte-aligned tail is 00 00 FF FF) and starts the next one from a fresh state, so a stream
+// cut by full flushes is a chain of independent raw bodies, each exactly what a one-shot deflate of its bytes
+// writes, but for its end.  k_marker_ordered lists the markers of the file; seg_merge decodes every segment
+// start of the eligible records in one launch of k_inflate's SEG variant and replaces a record whose chain
+// completes by its segments.
+static int markers_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, MarkerList& M) {
+  M.pos.clear();
+  M.kernel_ms = 0;
+  if (!F) return 0;
+  auto launch = [&](uint32_t nb, uint64_t seg, uint32_t* cnt, const uint64_t* base, uint64_t* dst, int write) {
+    hipLaunchKernelGGL(k_marker_ordered, dim3(nb), dim3(256), 0, c->st, d_file, F, seg, cnt, base, dst, write);
+  };
+  return ordered_list_dev(c, F, "k_marker_ordered", launch, M.pos, &M.kernel_ms);
+}
+
+// Eligible: a raw record (type 24-26; its body is the record), or a zlib record whose header says window 15 and
+// that is not stitched (its body lies between the 2 header bytes and the 4 trailer bytes), with a marker q,
+// body_start <= q and q + 4 < body_end.  Jobs: body_start and every such q + 4, each offered the bytes up to
+// body_end, without output (the record's whole decode lies in the arena, or is inflated again).  The chain
+// s_0 = body_start, s_{i+1} = s_i + consumed_i over jobs that ended at a marker with output completes when it
+// reaches a job that ended at a final block exactly at body_end, after at least one marker, with the outputs
+// summing to the record's; then the record is replaced, in place, by Rec{s_i, consumed_i, produced_i, 24 +
+// hint} (a raw parent's hint; a zlib parent's FLEVEL 0, 1 -> fast, 2 -> none, 3 -> max), flags bit 7 on all
+// but the last, and a last segment without output makes no record.  All or nothing.  c->recs keeps its capacity.
+static int seg_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, const MarkerList& M) {
+  auto tm_ = std::chrono::steady_clock::now();
+  const std::vector<Rec>& ref = c->recs;
+  struct Elig { size_t rec; uint64_t b0, b1; size_t j0, j1; };
+  std::vector<Elig> el;
+  std::vector<InfJob> jobs;
+  for (size_t i = 0; i < ref.size() && !M.pos.empty(); i++) {
+    const Rec& r = ref[i];
+    uint64_t b0 = r.offset, b1 = r.offset + r.comp_len;
+    if (r.type < 24) {
+      if (r.stitch != ~0ull || r.comp_len < 7 || (h[r.offset] >> 4) != 7) continue;
+      b0 += 2; b1 -= 4;
+    } else if (r.type > 26) continue;
+    auto it = std::lower_bound(M.pos.begin(), M.pos.end(), b0);
+    if (it == M.pos.end() || *it + 4 >= b1) continue;
+    Elig e{i, b0, b1, jobs.size(), 0};
+    jobs.push_back({b0, b1 - b0, NO_OUT, 0});
+    for (; it != M.pos.end() && *it + 4 < b1; ++it) jobs.push_back({*it + 4, b1 - (*it + 4), NO_OUT, 0});
+    e.j1 = jobs.size();
+    el.push_back(e);
+  }
+  const double infl0 = c->stats.k_inflate_ms;
+  std::vector<InfRes> res;
+  if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, 0, true, true, INF_SEG)) return r;
+  std::vector<Rec> merged;
+  merged.reserve(ref.size() + jobs.size());
+  size_t i = 0, chains = 0, made = 0;
+  for (const Elig& e : el) {
+    const Rec& par = ref[e.rec];
+    std::vector<Rec> segs;
+    const int type = par.type >= 24 ? par.type : (h[par.offset + 1] >> 6) == 2 ? 24 : (h[par.offset + 1] >> 6) == 3 ? 26 : 25;
+    uint64_t s = e.b0, sum = 0;
+    size_t k = 0;
+    bool ok = false;
+    for (size_t j = e.j0; j < e.j1;) {
+      const InfRes& r = res[j];
+      if (r.status != INF_END) break;
+      const uint64_t ao = par.arena_off != ~0ull ? par.arena_off + sum : ~0ull;
+      k++;
+      if (r.err & INF_AT_MARKER) {
+        if (r.produced < 1) break;
+        segs.push_back(Rec{s, r.consumed, r.produced, type, 128u, ao});
+        s += r.consumed; sum += r.produced;
+        // the job that starts at s (none: the marker's end is body_end, so no final block follows)
+        j = (size_t)(std::lower_bound(jobs.begin() + j + 1, jobs.begin() + e.j1, s,
+                                      [](const InfJob& x, uint64_t v) { return x.in_off < v; }) - jobs.begin());
+        if (j < e.j1 && jobs[j].in_off != s) break;
+        continue;
+      }
+      if (s + r.consumed != e.b1) break;
+      if (r.produced) segs.push_back(Rec{s, r.consumed, r.produced, type, 0u, ao});
+      sum += r.produced;
+      ok = k >= 2 && sum == par.infl_len;
+      break;
+    }
+    if (!ok) continue;
+    while (i < e.rec) merged.push_back(ref[i++]);
+    i++;   // the parent leaves
+    merged.insert(merged.end(), segs.begin(), segs.end());
+    chains++; made += segs.size();
+  }
+  while (i < ref.size()) merged.push_back(ref[i++]);
+  if (timing_on())
+    std::fprintf(stderr, "atz: k_marker_ordered: %zu markers, kernels %.3f ms (both passes), %zu eligible records, "
+                 "%zu jobs, k_inflate %.3f ms, %zu chains completed, %zu segments made\n", M.pos.size(), M.kernel_ms,
+                 el.size(), jobs.size(), c->stats.k_inflate_ms - infl0, chains, made);
+  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
+  if (chains) c->recs.assign(merged.begin(), merged.end());
+  TMARK("scan: flush segments");
+  return 0;
+}
+
 // the last four bytes of record r's stream (its Adler-32 trailer, big-endian) from the host copy h: a
 // stitched record's may straddle its pieces
 static uint32_t rec_trailer(const atz_ctx* c, const Rec& r, const uint8_t* h) {
@@ -1777,13 +1888,19 @@ static int scan_impl(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64
   pl.pos.clear();
   if (c->probe_mask)
     if (int r = probe_dev(c, d_file, F, pl)) return r;
+  MarkerList& ml = c->marks;
+  ml.pos.clear();
+  if (c->seg_mask)   // (one more record per marker at the most)
+    if (int r = markers_dev(c, d_file, F, ml)) return r;
   c->st_off.clear(); c->st_len.clear();
-  c->recs.reserve(S.max_records() + rc.size() + sp.cands.size() + pl.pos.size());
+  c->recs.reserve(S.max_records() + rc.size() + sp.cands.size() + pl.pos.size() + ml.pos.size());
   if (int r = scan_piece(c, h, d_file, S, 0, (uint32_t)S.chunks.size())) return r;
   if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), rc)) return r;
   if (int r = stitch_merge(c, d_file, S.arena_cap, S.fjobs.empty() && rc.empty(), sp)) return r;
   if (c->probe_mask)
     if (int r = probe_merge(c, d_file, F, S.arena_cap, S.fjobs.empty() && rc.empty() && sp.cands.empty(), pl)) return r;
+  if (c->seg_mask)
+    if (int r = seg_merge(c, h, d_file, ml)) return r;
   c->stats.scan_ms = ms_since(t0);
   return 0;
 }
@@ -1808,8 +1925,8 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
   // Streams whose scan decode kept its full output in the arena are copied; the others are
   // inflated again from the file with their exact length (doInflate, main.cpp:461-486) -- the
   // same bytes from the same offset, so both give the same result.
-  std::vector<InfJob> jobs, raw_jobs, st_jobs;
-  std::vector<size_t> job_rec, raw_rec, st_rec;
+  std::vector<InfJob> jobs, raw_jobs, st_jobs, seg_jobs;
+  std::vector<size_t> job_rec, raw_rec, st_rec, seg_rec;
   std::vector<Seg> segs;
   for (size_t s = r0; s < r1; s++) {
     const Rec& r = c->recs[s];
@@ -1820,8 +1937,10 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
       InfJob jb;
       jb.in_off = r.offset; jb.in_len = r.comp_len; jb.out_off = loc[s - r0]; jb.out_cap = r.infl_len;
       if (r.stitch != ~0ull) jb.in_off = r.stitch;   // (its input base is the stitch buffer)
-      (r.stitch != ~0ull ? st_jobs : r.type >= 24 ? raw_jobs : jobs).push_back(jb);
-      (r.stitch != ~0ull ? st_rec : r.type >= 24 ? raw_rec : job_rec).push_back(s);
+      // (flags bit 7: a flush-terminated segment of the segment extension, which ends at its marker)
+      const bool seg = r.type >= 24 && (r.flags & 128u);
+      (r.stitch != ~0ull ? st_jobs : seg ? seg_jobs : r.type >= 24 ? raw_jobs : jobs).push_back(jb);
+      (r.stitch != ~0ull ? st_rec : seg ? seg_rec : r.type >= 24 ? raw_rec : job_rec).push_back(s);
     }
   }
   if (!segs.empty()) {
@@ -1843,6 +1962,13 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
     jobs.insert(jobs.end(), raw_jobs.begin(), raw_jobs.end());
     job_rec.insert(job_rec.end(), raw_rec.begin(), raw_rec.end());
     res.insert(res.end(), rres.begin(), rres.end());
+  }
+  if (!seg_jobs.empty()) {   // flush-terminated segments (the segment extension): the decoder that stops at a marker
+    std::vector<InfRes> gres;
+    if (int r = run_inflate_jobs(c, d_file, slab.as<uint8_t>(), seg_jobs, gres, 0, false, true, INF_SEG)) return r;
+    jobs.insert(jobs.end(), seg_jobs.begin(), seg_jobs.end());
+    job_rec.insert(job_rec.end(), seg_rec.begin(), seg_rec.end());
+    res.insert(res.end(), gres.begin(), gres.end());
   }
   if (!st_jobs.empty()) {   // stitched records (the stitch extension): from their contiguous copies
     std::vector<InfRes> sres;
@@ -2278,9 +2404,11 @@ static uint32_t mw_cap_for(size_t n_streams) {
 static bool mw_trial(const Pipe* c, int kind, uint32_t memlevel) { return kind != 0 && memlevel <= c->mw_cap; }
 // the kernel a trial of kind k runs on: bit 0 multi-wave, bits 1-2 its strategy (Trial::host & TH_STRAT:
 // 1 Z_FILTERED on the slow kind, 3 Z_RLE / 2 Z_HUFFMAN_ONLY on the table-less kind 0)
-// bit 3: the GNU deflater family (Trial::host & TH_GNU), always single-wave
+// bit 3: the GNU deflater family (Trial::host & TH_GNU), always single-wave; bit 4: the flush-capable kernels
+// (Trial::host & TH_FLUSH), default strategy, single- or multi-wave
 static uint32_t trial_variant(const Pipe* c, int k, const Trial& t) {
   if (t.host & TH_GNU) return 8u;
+  if (t.host & TH_FLUSH) return 16u | (mw_trial(c, k, t.memlevel) ? 1u : 0u);
   return (mw_trial(c, k, t.memlevel) ? 1u : 0u) | ((t.host & TH_STRAT) << 1);
 }
 // (memlevel 0: a GNU-family trial, whose blocks hold up to 32 767 symbols whatever the stream's tables)
@@ -2293,6 +2421,9 @@ static uint64_t sym_words(const Pipe* c, int kind, uint32_t memlevel, uint64_t n
 struct TrialBatch {
   std::vector<Trial> tr[3];
   uint64_t out_tot = 0, sym_tot = 0;
+  // the raw pass of a context with the segment mask: every default-strategy zlib trial goes to the flush-capable
+  // kernels (TH_FLUSH), so that a list step's flush-terminated and finished trials share their launches
+  bool flush_kernels = false;
   // A trial of stream s (len inflated bytes) at (level, window, memLevel) under zlib strategy strat.
   // Z_RLE and Z_HUFFMAN_ONLY ignore the level and read no tables (the stored kind's kernels); Z_FILTERED
   // only changes deflate_slow, so on levels 1-3 it is the default strategy.  m == 0: a GNU-family trial (level
@@ -2304,9 +2435,10 @@ struct TrialBatch {
     const int kind = cl == 0 || strat >= 2 ? 0 : cl <= 3 ? 1 : 2;
     Trial t{};
     t.stream = s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)(m ? m : 8);
-    t.mode = mode; t.host = strat | (m ? 0u : (uint32_t)TH_GNU);
+    t.mode = mode; t.host = strat | (m ? 0u : (uint32_t)TH_GNU) |
+                              ((mode & TM_FLUSH) || (flush_kernels && (mode & TM_RAW) && !strat && m) ? (uint32_t)TH_FLUSH : 0u);
     t.best_ident = best_ident;
-    t.out_off = out_tot; t.out_cap = bound(len, w, m) + 64;
+    t.out_off = out_tot; t.out_cap = bound(len, w, m) + 64 + ((mode & TM_FLUSH) ? 5 : 0);
     out_tot += (t.out_cap + 255) & ~255ull;
     t.sym_off = sym_tot; sym_tot += sym_words(c, kind, (uint32_t)m, len);
     tr[kind].push_back(t);
@@ -2340,7 +2472,7 @@ static void trials_order(atz_ctx* x, const Pipe* c, std::vector<Trial>* in, Tria
     bool strat = false;   // strategy trials among them
     for (size_t q = 0; q < n; q++) {
       const Trial& t = in[k][q];
-      strat |= (t.host & (TH_STRAT | TH_GNU)) != 0;
+      strat |= (t.host & (TH_STRAT | TH_GNU | TH_FLUSH)) != 0;
       const uint64_t w = x->recs[t.stream].infl_len * (uint64_t)(k == 1 ? 3 : 1) * (uint64_t)(10 - t.memlevel) *
                          (uint64_t)((t.mode & TM_REPLAY) ? 1 : 4);   // replays skip the match walks
       const uint64_t mw = k != 0 && t.memlevel <= mwm;
@@ -2388,6 +2520,11 @@ static int trials_launch(atz_ctx* x, Pipe* c, const uint8_t* d_cmp, const SweepO
       {2, 1, false, k_trial_slow_filt, "k_trial_slow_filt"},
       {1, 4, false, k_trial_fast_gnu, "k_trial_fast_gnu"},   // (strat 4: trial_variant's bit 3, the GNU family)
       {2, 4, false, k_trial_slow_gnu, "k_trial_slow_gnu"},
+      {0, 8, false, k_trial_stored_flush, "k_trial_stored_flush"},   // (strat 8: trial_variant's bit 4, TH_FLUSH)
+      {1, 8, true, k_trial_fast_flush_mw, "k_trial_fast_flush"},
+      {1, 8, false, k_trial_fast_flush, "k_trial_fast_flush"},
+      {2, 8, true, k_trial_slow_flush_mw, "k_trial_slow_flush"},
+      {2, 8, false, k_trial_slow_flush, "k_trial_slow_flush"},
   };
   for (size_t i = 0; i < cnt; i++)   // a waiting trial or a duplicate never reaches a launch
     if (h[i].host & (TH_WAITS | TH_DUP)) return ATZ_E_INTERNAL;
@@ -3703,7 +3840,7 @@ static void strategy_list(std::vector<uint32_t>& l, int type, uint32_t mask) {
 // batch builds the bucket tables its filtered trials read, as deflate_dev does).  A stream the pass
 // records gets clevel = strategy << 4 | level; the others keep what the reference walk left.
 // raw: the same pass over the container extension's records (raw_list; TM_RAW trials), see raw_pass.
-static void raw_list(std::vector<uint32_t>& l, int type, uint32_t defl_mask);
+static void raw_list(std::vector<uint32_t>& l, int type, uint32_t defl_mask, bool flush);
 // the memLevel whose bucket and match tables a list entry's trial reads (memLevel 0, a GNU candidate: 8)
 static int tab_memlevel(uint32_t q) { return (q & 0xff) ? (int)(q & 0xff) : 8; }
 static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss, bool raw) {
@@ -3722,7 +3859,7 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
   size_t longest = 0;
   for (size_t s = 0; s < n; s++) {
     if (ss[s].recomp || c->recs[s].infl_len >= (1ull << 31)) continue;
-    if (raw) raw_list(ex[s].list, c->recs[s].type, c->defl_mask);
+    if (raw) raw_list(ex[s].list, c->recs[s].type, c->defl_mask, (c->recs[s].flags & 128u) != 0);
     else strategy_list(ex[s].list, c->recs[s].type, c->strat_mask);
     if (ex[s].list.empty()) continue;
     todo.push_back((uint32_t)s);
@@ -3761,11 +3898,13 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
       }
       if (int r = private_chains(c, p, need)) return r;
       TrialBatch B;   // never saves, replays or stands for a duplicate
+      B.flush_kernels = raw && c->seg_mask;
       for (size_t a = a0; a < a1; a++) {
         const uint32_t s = act[a], q = ex[s].list[j];
         const int m = (int)(q & 0xff);
         const auto at = B.add(p, s, c->recs[s].infl_len, (int)((q >> 16) & 0xff), (int)((q >> 8) & 0xff), m, (q >> 24) & 3,
-                              raw ? TM_RAW : 0, std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len)));
+                              raw ? (uint8_t)(TM_RAW | ((q >> 30) & 1u ? TM_FLUSH : 0)) : 0,
+                              std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len)));
         if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][tab_memlevel(q)];
       }
       if (int r = B.reserve(p)) return r;
@@ -3809,7 +3948,8 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
     if (!(e.ident > 0 && C - e.ident <= c->o.recomp_tresh)) continue;   // main.cpp:454
     StreamState& st = ss[s];
     st.c = (uint8_t)((((e.best >> 28) & 1u) << 6) | (((e.best >> 24) & 3u) << 4) | ((e.best >> 16) & 0xff));
-    st.w = (uint8_t)((e.best >> 8) & 0xff); st.m = (uint8_t)(e.best & 0xff);
+    st.w = (uint8_t)(((e.best >> 8) & 0xff) | (((e.best >> 30) & 1u) << 7));   // (bit 7: flush-terminated)
+    st.m = (uint8_t)(e.best & 0xff);
     st.ident = e.ident;
     st.rawdiff.swap(e.rawdiff); st.diffval.swap(e.diffval);
     st.first_diff = st.rawdiff.empty() ? -1 : (int64_t)st.rawdiff[0];
@@ -3842,21 +3982,25 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
 // defl_mask bit 0 (atz_set_deflaters): GNU gzip's and Info-ZIP's deflater, levels 1-9 in the
 // hint's order, marked with memLevel 0, directly behind the memLevel-8 group (their parse is zlib's at
 // memLevel 8, so they share its tables) -- 99 entries.
-static void raw_list(std::vector<uint32_t>& l, int type, uint32_t defl_mask) {
+// flush (a record with flags bit 7, the segment extension's): every entry carries bit 30, which
+// makes its trial TM_FLUSH, and no GNU candidate is added (gzip has no full flush) -- 90 entries.
+static void raw_list(std::vector<uint32_t>& l, int type, uint32_t defl_mask, bool flush) {
   if (type < 24 || type > 26) return;
+  if (flush) defl_mask = 0;
+  const uint32_t fb = flush ? 1u << 30 : 0u;
   static const int mo[9] = {8, 9, 7, 6, 5, 4, 3, 2, 1};
   static const int lo[3][10] = {{6, 9, 1, 5, 7, 8, 4, 3, 2, 0},    // no hint
                                 {1, 2, 3, 4, 5, 6, 7, 8, 9, 0},    // fast
                                 {9, 8, 7, 6, 5, 4, 3, 2, 1, 0}};   // max
   for (int m : mo) {
-    for (int cl : lo[type - 24]) l.push_back((1u << 28) | pk(cl, 15, m));
+    for (int cl : lo[type - 24]) l.push_back(fb | (1u << 28) | pk(cl, 15, m));
     if (m == 8 && (defl_mask & 1u))
       for (int cl : lo[type - 24])
         if (cl) l.push_back((1u << 28) | pk(cl, 15, 0));
   }
 }
 static int raw_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
-  return (c->cont_mask || c->probe_mask) ? ext_pass(c, d_file, ss, true) : 0;
+  return (c->cont_mask || c->probe_mask || c->seg_mask) ? ext_pass(c, d_file, ss, true) : 0;
 }
 
 // the sweep of every record of the context (atz_sweep)
@@ -3950,6 +4094,7 @@ static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<
 // version 2 (the strategy extension): some descriptor's clevel byte is strategy << 4 | level;
 // version 3 (the container extension): some descriptor's is raw << 6 | strategy << 4 | level
 // version 5 (the deflater extension): some raw descriptor's memLevel byte is 0, a GNU-family body
+// version 6 (the segment extension): some raw descriptor's window byte is 0x8F, a flush-terminated body
 static void atz_header(std::vector<uint8_t>& meta, uint64_t F, uint64_t nrec, uint8_t version = 1) {
   const uint8_t h[4] = {'A', 'T', 'Z', version};
   meta.insert(meta.end(), h, h + 4);
@@ -3969,7 +4114,8 @@ static int write_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::
     nrec += ss[s].recomp;
     if (ss[s].recomp && (ss[s].c >> 4)) version = std::max<uint8_t>(version, (ss[s].c & 0x40) ? 3 : 2);
     if (ss[s].recomp && c->recs[s].stitch != ~0ull) version = std::max<uint8_t>(version, 4);
-    if (ss[s].recomp && (ss[s].c & 0x40) && ss[s].m == 0) version = 5;   // a GNU-family body (memLevel byte 0)
+    if (ss[s].recomp && (ss[s].c & 0x40) && ss[s].m == 0) version = std::max<uint8_t>(version, 5);   // a GNU-family body (memLevel byte 0)
+    if (ss[s].recomp && (ss[s].w & 0x80)) version = 6;   // a flush-terminated segment (window byte 0x8F)
     npieces += c->recs[s].stitch != ~0ull ? c->recs[s].pk : 1;
   }
   atz_header(meta, F, nrec, version);
@@ -4029,8 +4175,10 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   }
   if (c->probe_mask)   // (the probe extension's survivors, likewise: each may become a record)
     if (int r = probe_dev(c, d_file, F, c->probe)) return r;
+  if (c->seg_mask)     // (the segment extension's markers: each may add a record)
+    if (int r = markers_dev(c, d_file, F, c->marks)) return r;
   const size_t n_max = S.max_records() + raw_cands.size() + stitch_plan.cands.size() +
-                       (c->probe_mask ? c->probe.pos.size() : 0);
+                       (c->probe_mask ? c->probe.pos.size() : 0) + (c->seg_mask ? c->marks.pos.size() : 0);
   c->recs.reserve(n_max);
   std::vector<StreamState>& ss = c->ss_keep;
   SweepRun R;
@@ -4056,9 +4204,9 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   });
   struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join_begin{t_begin};
   double scan_busy = ms_since(t0);
-  // (with a container, stitch or probe mask the added records need the reference's final ones: scan, merge,
-  // then sweep)
-  const bool spec = P == 1 && spec_cont_on() && !ext_anchor_mask(c) && !c->probe_mask;
+  // (with a container, stitch, probe or segment mask the added records need the reference's final ones: scan,
+  // merge, then sweep)
+  const bool spec = P == 1 && spec_cont_on() && !ext_anchor_mask(c) && !c->probe_mask && !c->seg_mask;
   if (spec) {
     // The first continuations of pending streams (each a decode of the stream from its header through
     // the chunk boundary) are latency-bound: one small launch, 15-30 ms.  The records do not wait for
@@ -4129,6 +4277,8 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
       if (int r = probe_merge(c, d_file, F, S.arena_cap,
                               S.fjobs.empty() && raw_cands.empty() && stitch_plan.cands.empty(), c->probe))
         return r;
+    if (c->seg_mask)
+      if (int r = seg_merge(c, h, d_file, c->marks)) return r;
     if (p == 0) {
       t_begin.join();
       if (rc_begin) return rc_begin;
@@ -4202,7 +4352,8 @@ static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std:
     }
     c->chain_off.assign(n, {});
     std::vector<std::pair<uint32_t, int>> need;
-    // (params carry a strategy in bits 24-25: Z_RLE and Z_HUFFMAN_ONLY read no bucket tables; bit 28: raw output)
+    // (params carry a strategy in bits 24-25: Z_RLE and Z_HUFFMAN_ONLY read no bucket tables; bit 28: raw output;
+    // bit 30: a flush-terminated body, TM_FLUSH)
     for (size_t s = s0; s < s1; s++)
       if (((params[s] >> 16) & 0xff) > 0 && ((params[s] >> 24) & 3) < 2) need.push_back({(uint32_t)s, mlev(s) ? mlev(s) : 8});
     if (int r = private_chains(c, p, need)) return r;
@@ -4210,7 +4361,8 @@ static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std:
     for (size_t s = s0; s < s1; s++) {
       const int m = mlev(s);
       const auto at = B.add(p, (uint32_t)s, len[s], (int)((params[s] >> 16) & 0xff), (int)((params[s] >> 8) & 0xff), m,
-                            (params[s] >> 24) & 3, (uint8_t)(TM_FULL | ((params[s] >> 28) & 1u ? TM_RAW : 0)), 0);
+                            (params[s] >> 24) & 3,
+                            (uint8_t)(TM_FULL | ((params[s] >> 28) & 1u ? TM_RAW : 0) | ((params[s] >> 30) & 1u ? TM_FLUSH : 0)), 0);
       if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m ? m : 8];
     }
     if (int r = B.reserve(p)) return r;
@@ -4299,8 +4451,11 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
   // of bits 6 and 7; a stitched descriptor's piece list follows its payload: u32 k, k x u32 lengths)
   // version 5: the deflater extension's (version 4's, and a raw descriptor with the default strategy, level 1-9
   // and memLevel byte 0 is a GNU-family body)
-  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 5) return ATZ_E_FORMAT;   // main.cpp:1018-1021
-  const bool v5 = atz[3] == 5;
+  // version 6: the segment extension's (version 5's, and a raw descriptor with the default strategy, memLevel
+  // 1-9 and window byte 0x8F is a flush-terminated body of window 15)
+  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 6) return ATZ_E_FORMAT;   // main.cpp:1018-1021
+  const bool v6 = atz[3] == 6;
+  const bool v5 = atz[3] == 5 || v6;
   const bool v2 = atz[3] == 2, v4 = atz[3] == 4 || v5, v3 = atz[3] == 3 || v4;
   if (rd8(atz + 4) != n) return ATZ_E_FORMAT;                              // main.cpp:1022-1025
   origlen = rd8(atz + 12);
@@ -4353,6 +4508,10 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
     } else if (x.c > 9) return ATZ_E_REF_ABORT;
     if (v5 && x.m == 0) {   // GNU's: raw, not stitched (bit 7 was read above), default strategy, level 1-9, window 15
       if ((x.c & 0xf0) != 0x40 || (x.c & 15) < 1 || x.w != 15 || x.k) return ATZ_E_REF_ABORT;
+      continue;
+    }
+    if (v6 && (x.w & 0x80)) {   // flush-terminated: window 15, raw, not stitched, default strategy, memLevel 1-9
+      if (x.w != 0x8f || (x.c & 0xf0) != 0x40 || x.k || x.m < 1 || x.m > 9) return ATZ_E_REF_ABORT;
       continue;
     }
     if (x.w < 8 || x.w > 15 || x.m < 1 || x.m > 9) return ATZ_E_REF_ABORT;
@@ -4423,8 +4582,9 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
       if (d[j].il) segs.push_back({2, 0, d[j].ipos, loc[j], d[j].il});
       addr[j] = (uint64_t)(uintptr_t)slab.p + loc[j];
       len[j] = d[j].il;
-      const int w = d[j].w == 8 ? 9 : d[j].w;
-      params[j] = ((uint32_t)((d[j].c >> 6) & 1) << 28) | ((uint32_t)((d[j].c >> 4) & 3) << 24) |
+      const int w = d[j].w == 8 ? 9 : d[j].w & 0x7f;
+      params[j] = ((uint32_t)(d[j].w >> 7) << 30) |   // a flush-terminated body (parse_atz: version 6 only)
+                  ((uint32_t)((d[j].c >> 6) & 1) << 28) | ((uint32_t)((d[j].c >> 4) & 3) << 24) |
                   ((uint32_t)(d[j].c & 15) << 16) | ((uint32_t)w << 8) | d[j].m;
       if (d[j].m == 0) params[j] |= 1u << 29;   // a GNU-family body (parse_atz: version 5 only)
     }
@@ -4994,7 +5154,8 @@ int atz_deflate(atz_ctx_t* c, const uint8_t* in, uint64_t in_len, int clevel, in
   });
 }
 
-// ex: params carry zlib's strategy in bits 24-27, the raw flag in bit 28 and the GNU deflater in bit 29 (atz_deflate_batch_ex); else
+// ex: params carry zlib's strategy in bits 24-27, the raw flag in bit 28, the GNU deflater in bit 29 and the flush
+// end in bit 30 (atz_deflate_batch_ex); else
 // bits 16-31 are the level
 static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
                              const uint32_t* params, uint64_t n, uint8_t* out, const uint64_t* out_offs,
@@ -5008,17 +5169,19 @@ static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, con
       if (offs[k] + lens[k] > len) return ATZ_E_ARG;
       const uint32_t raw = ex ? (params[k] >> 28) & 1u : 0u;   // no zlib header, no Adler-32 trailer
       const uint32_t gnu = ex ? (params[k] >> 29) & 1u : 0u;   // the GNU deflater family: raw, window 15, level 1-9 only
-      const int sg = ex ? (int)((params[k] >> 24) & ~(16u | 32u)) : 0;
+      const uint32_t fl = ex ? (params[k] >> 30) & 1u : 0u;    // a flush-terminated body: raw, zlib's, default strategy only
+      const int sg = ex ? (int)((params[k] >> 24) & ~(16u | 32u | 64u)) : 0;
       int cl = (int)(ex ? (params[k] >> 16) & 0xff : params[k] >> 16), w = (int)((params[k] >> 8) & 0xff), m = (int)(params[k] & 0xff);
       if (gnu) {   // (the memLevel field is ignored)
         if (!raw || sg != 0 || w != 15 || cl < 1 || cl > 9) return ATZ_E_ARG;
         m = 0;
       } else if (m < 1 || m > 9) return ATZ_E_ARG;
+      if (fl && (!raw || gnu || sg != 0 || w < 9)) return ATZ_E_ARG;
       if (cl < 0 || cl > 9 || w < 8 || w > 15) return ATZ_E_ARG;
       if (sg > 3 || (sg >= 2 && cl < 1)) return ATZ_E_ARG;   // Z_FIXED is not supported; Z_RLE / Z_HUFFMAN_ONLY have no level 0
       if (w == 8) w = 9;
       ins[k] = {buf + offs[k], lens[k]};
-      ps[k] = (gnu << 29) | (raw << 28) | ((uint32_t)sg << 24) | ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
+      ps[k] = (fl << 30) | (gnu << 29) | (raw << 28) | ((uint32_t)sg << 24) | ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
     }
     std::vector<std::vector<uint8_t>> outs;
     if (int r = deflate_many(c, ins, ps, outs)) return r;
@@ -5108,6 +5271,31 @@ int atz_set_deflaters(atz_ctx_t* c, uint32_t mask) {
   return ATZ_OK;
 }
 
+int atz_set_segments(atz_ctx_t* c, uint32_t mask) {
+  if (!c || (mask & ~1u)) return ATZ_E_ARG;   // bit 0: full-flush points
+  c->seg_mask = mask;
+  c->scan_valid = false;
+  return ATZ_OK;
+}
+
+int atz_flush_markers(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint64_t** out, uint64_t* n) {
+  return guarded([&]() -> int {
+    (void)hipGetLastError();
+    if (!c || (!file && len) || !out || !n) return ATZ_E_ARG;
+    c->scan_valid = false; c->shard.stage = 0;   // d_file is replaced
+    if (int r = upload(c, c->d_file, file, len)) return r;
+    MarkerList ml;
+    if (int r = markers_dev(c, c->d_file.as<uint8_t>(), len, ml)) return r;
+    if (timing_on())
+      std::fprintf(stderr, "atz: k_marker_ordered: %zu markers, kernels %.3f ms (both passes)\n", ml.pos.size(), ml.kernel_ms);
+    *out = (uint64_t*)std::malloc((ml.pos.size() + 1) * 8);
+    if (!*out) return ATZ_E_NOMEM;
+    if (!ml.pos.empty()) std::memcpy(*out, ml.pos.data(), ml.pos.size() * 8);
+    *n = ml.pos.size();
+    return ATZ_OK;
+  });
+}
+
 int atz_probe_positions(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint64_t** out, uint64_t* n) {
   return guarded([&]() -> int {
     (void)hipGetLastError();
@@ -5138,11 +5326,13 @@ int atz_stitch_pieces(atz_ctx_t* c, uint64_t record, uint64_t** offs, uint64_t**
   });
 }
 
-int atz_inflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
-                      uint64_t n, uint32_t* status, uint64_t* consumed, uint64_t* produced) {
+// seg: k_inflate's SEG variant on raw bodies (atz_inflate_segments); at_marker[k]: job k ended at a flush marker
+static int inflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
+                             uint64_t n, uint32_t* status, uint64_t* consumed, uint64_t* produced, bool seg,
+                             uint8_t* at_marker) {
   return guarded([&]() -> int {
     (void)hipGetLastError();
-    if (!c || (!buf && len)) return ATZ_E_ARG;
+    if (!c || (!buf && len) || (seg && !at_marker)) return ATZ_E_ARG;
     c->scan_valid = false; c->shard.stage = 0;   // the arena holds the last scan's kept outputs
     if (int r = upload(c, c->d_tmp, buf, len)) return r;
     std::vector<InfJob> jobs(n);
@@ -5153,10 +5343,23 @@ int atz_inflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint
     }
     std::vector<InfRes> res;
     const uint64_t arena_cap = cap_bytes(std::min<uint64_t>(64ull << 30, std::max<uint64_t>(256ull << 20, n * ARENA_SLOT)));
-    if (int r = run_inflate_jobs(c, c->d_tmp.as<uint8_t>(), nullptr, jobs, res, arena_cap)) return r;
-    for (uint64_t k = 0; k < n; k++) { status[k] = res[k].status; consumed[k] = res[k].consumed; produced[k] = res[k].produced; }
+    if (int r = run_inflate_jobs(c, c->d_tmp.as<uint8_t>(), nullptr, jobs, res, arena_cap, false, true, seg ? INF_SEG : 0)) return r;
+    for (uint64_t k = 0; k < n; k++) {
+      status[k] = res[k].status; consumed[k] = res[k].consumed; produced[k] = res[k].produced;
+      if (seg) at_marker[k] = res[k].status == INF_END && (res[k].err & INF_AT_MARKER) ? 1 : 0;
+    }
     return ATZ_OK;
   });
+}
+
+int atz_inflate_batch(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
+                      uint64_t n, uint32_t* status, uint64_t* consumed, uint64_t* produced) {
+  return inflate_batch_api(c, buf, len, offs, lens, n, status, consumed, produced, false, nullptr);
+}
+
+int atz_inflate_segments(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
+                         uint64_t n, uint32_t* status, uint64_t* consumed, uint64_t* produced, uint8_t* at_marker) {
+  return inflate_batch_api(c, buf, len, offs, lens, n, status, consumed, produced, true, at_marker);
 }
 
 int atz_shard_scan(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, uint64_t len, int rank, int world,
@@ -5164,7 +5367,7 @@ int atz_shard_scan(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, u
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !blob || !blob_len || world < 1 || rank < 0 || rank >= world) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
+    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask || c->seg_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
     dev_mark_call();   // (the peak runs on through atz_shard_sweep, whose stats report it)
     std::vector<uint64_t> b;
     if (int r = shard_scan_impl(c, d_file, h_file, len, rank, world, b)) { c->shard.stage = 0; return r; }
@@ -5182,7 +5385,7 @@ int atz_shard_sweep(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, 
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !piece_len || !recomp_flags || !n_flags || !n_recomp) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask) return ATZ_E_ARG;
+    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask || c->seg_mask) return ATZ_E_ARG;
     std::vector<uint8_t> f;
     if (int r = shard_sweep_impl(c, d_file, h_file, len, blobs, blob_lens, world, f, n_recomp)) {
       c->shard.stage = 0;

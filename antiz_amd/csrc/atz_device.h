@@ -30,6 +30,8 @@ enum : uint32_t { INF_END = 0, INF_ERROR = 1, INF_NEED = 2, INF_RETRY = 3 };   /
 // trials); the low bits are the failing check's code
 static constexpr uint32_t INF_HINT_NOSHORT = 1u << 31;
 static constexpr uint32_t INF_HINT_MLEV_SHIFT = 27;
+// bit 26 (k_inflate's SEG variant only): the job ended at a flush marker, not at a final block
+static constexpr uint32_t INF_AT_MARKER = 1u << 26;
 
 struct InfRes {
   uint32_t status;    // INF_*
@@ -54,6 +56,8 @@ enum : uint8_t {
   TM_REPLAY = 8,      // replays the rp_nsym symbols saved at rp_syms instead of parsing
   TM_CHECKED = 16,    // with TM_REPLAY: only if its own match table equals the one saved at rp_tab (else it parses)
   TM_SAVE_TAB = 32,   // with TM_SAVE: records the match-table entries its parse reads at rp_tab
+  TM_FLUSH = 64,      // with TM_RAW: the body ends as a full flush ends it (no final block; the empty stored block's
+                      // marker).  Only the k_trial_*_flush kernels test it (TH_FLUSH puts a trial there)
   TM_RP_SYMS = TM_SAVE | TM_REPLAY,        // rp_syms is read or written
   TM_RP_TAB = TM_CHECKED | TM_SAVE_TAB,    // rp_tab is read or written
 };
@@ -62,6 +66,8 @@ enum : uint32_t {
   TH_STRAT = 3,   // mask: zlib's strategy number (0 default, 1 Z_FILTERED, 2 Z_HUFFMAN_ONLY, 3 Z_RLE)
   TH_WAITS = 4,   // waits for a saver of this round (launched in the round's second set)
   TH_DUP = 8,     // a duplicate of an earlier trial's result: not launched
+  TH_FLUSH = 32,  // runs on the flush-capable kernels (k_trial_{stored,fast,slow}_flush and the two _mw ones):
+                  // every TM_FLUSH trial, and the other default-strategy raw trials of a context with the segment mask
   TH_GNU = 16,    // the GNU deflater family (k_trial_{fast,slow}_gnu): memlevel is 8, the symbol buffer 32 768 + 64
 };
 struct Trial {

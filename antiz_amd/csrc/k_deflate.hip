@@ -896,7 +896,8 @@ struct BitOut {
   uint64_t pos;      // bytes written
   uint64_t bb;       // pending bits (< 8 after every flush)
   uint32_t bc;
-  uint32_t raw;      // TM_RAW: no Adler-32 trailer (kept here, in the struct's padding, not in a register)
+  uint32_t raw;      // TM_RAW: no Adler-32 trailer (kept here, in the struct's padding, not in a register);
+                     // on the k_trial_*_flush kernels (FAM 2) also TM_FLUSH: the body ends as a full flush ends it
   // comparison against the original
   const GLOBAL uint8_t* orig;
   uint64_t clen;     // C_s
@@ -1101,6 +1102,13 @@ __device__ inline void windup(LDS BitOut& b, LDS uint32_t* stage, int lane) {  /
     emit_bytes_from_stage(b, stage, 1, lane);
     b.bb = 0; b.bc = 0;
   }
+}
+// what a full flush writes behind its last block (_tr_stored_block of nothing, not final, Z/trees.c:865-878):
+// three zero bits, padding to a byte, LEN 0 and NLEN 0xffff
+__device__ inline void flush_end(LDS BitOut& b, LDS uint32_t* stage, int lane) {
+  put_bits(b, stage, 0u, 3, lane);
+  windup(b, stage, lane);
+  put_bits(b, stage, 0xffff0000u, 32, lane);
 }
 
 // ---- Huffman tree construction, Z/trees.c:453-699 ----
@@ -1904,6 +1912,9 @@ __device__ __forceinline__ void spec_stop(const LDS TrialShared& s, const SweepA
   if (lane == 0) __hip_atomic_fetch_min((GLOBAL uint32_t*)(uintptr_t)a, uni(s.stop_j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// FL (TrialRun's FAM 2): a trial whose BitOut::raw holds TM_FLUSH ends as a full flush ends it: the block handed
+// over as the last is not final, absent when it holds no symbol, and the marker follows
+template <bool FL = false>
 __device__ void trial_flusher(const SweepArgs& A, LDS TrialShared& s, LDS MWPart& mw, const Trial& tr,
                               const GLOBAL uint32_t* syms, const GLOBAL uint8_t* in, uint32_t level, uint32_t lbs,
                               bool full_needed, int f, int lane) {
@@ -1937,8 +1948,17 @@ __device__ void trial_flusher(const SweepArgs& A, LDS TrialShared& s, LDS MWPart
     }
     if (!turn) break;
     const uint64_t c2 = clock64();
-    const uint32_t hz = uni(block_emit(me.k, stage, b, syms + sbase, in, bs, p, S, last_lit, lbs, last, A.o, tr.best_ident,
-                                       full_needed, pl.opt_lenb, pl.static_lenb, pl.lmax, pl.dmax, pl.max_blindex, lane));
+    uint32_t hz = 0;
+    if constexpr (FL) {
+      const bool fl = last && (uni(b.raw) & TM_FLUSH) != 0;
+      if (!fl || last_lit)
+        hz = uni(block_emit(me.k, stage, b, syms + sbase, in, bs, p, S, last_lit, lbs, fl ? 0 : last, A.o, tr.best_ident,
+                            full_needed, pl.opt_lenb, pl.static_lenb, pl.lmax, pl.dmax, pl.max_blindex, lane));
+      if (fl) flush_end(b, stage, lane);
+    } else {
+      hz = uni(block_emit(me.k, stage, b, syms + sbase, in, bs, p, S, last_lit, lbs, last, A.o, tr.best_ident,
+                          full_needed, pl.opt_lenb, pl.static_lenb, pl.lmax, pl.dmax, pl.max_blindex, lane));
+    }
     if (hz && lane == 0) __hip_atomic_fetch_or(&ctl.hazard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     uint32_t st = ~0u;
     if (last) {
@@ -1987,6 +2007,9 @@ static constexpr uint32_t TR_DECIDED = 0xfffffffeu;   // parser-side: a flusher 
 // deflate.c / trees.c: zlib's parse at memLevel 8, zlib's trees and emission, but ct_tally's
 // blocks -- a buffer of 32 768 symbols, and for levels above 2 a check at every 4 096th symbol of the block
 // that ends it early when matches are few and the block already halves its input (due / flush_here).
+// 2 zlib, on the kernels that can end a body as deflate(Z_FULL_FLUSH) ends a segment (Trial::host & TH_FLUSH;
+// DESIGN.md s7.6): parse, blocks and trees are FAM 0's; end_parse and the multi-wave flusher's last block read
+// TM_FLUSH at run time, so a masked context's raw pass runs flush-terminated and finished trials in one launch.
 template <int KIND, typename SH, int STRAT = 0, int FAM = 0>
 struct TrialRun {
   static constexpr bool MW = HasMW<SH>::value;
@@ -2050,7 +2073,7 @@ struct TrialRun {
     z.last_lit = 0; z.nsym = 0;
     if (wave == 0) {
       b.out = (GLOBAL uint8_t*)(A.out + tr.out_off); b.cap = tr.out_cap; b.pos = 0; b.bb = 0; b.bc = 0;
-      b.raw = tr.mode & TM_RAW;
+      b.raw = tr.mode & (FAM == 2 ? (TM_RAW | TM_FLUSH) : TM_RAW);
       b.orig = (const GLOBAL uint8_t*)(A.file + sd.orig_off); b.clen = sd.comp_len;
       b.shortcut = sd.comp_len > A.o.shortcut_len ? A.o.shortcut_len : 0;
       b.eq_all = 0; b.eq_sc = 0; b.overflow = 0;
@@ -3045,7 +3068,21 @@ struct TrialRun {
     else state = TR_DECIDED;
   } else if (state == ~0u) {
     saved_flags |= 1;   // every symbol tallied: a saving trial's sequence is complete
-    FLUSH(1);
+    if constexpr (FAM == 2) {
+      // TM_FLUSH (deflate(Z_FULL_FLUSH), Z/deflate.c:1616-1617, 1719-1720, 1850-1851 and 920-937): the last block
+      // is not final, and absent when nothing waits in it; the marker follows.  Read where BitOut::raw lives, and
+      // again behind the block: no register is held across it.
+      int lastb = 1;
+      bool emit = true;
+      if (uni(b.raw) & TM_FLUSH) {
+        lastb = 0;
+        emit = KIND == 0 ? z.p > z.block_start : z.last_lit != 0;
+      }
+      if (emit) FLUSH(lastb);
+      if (uni(b.raw) & TM_FLUSH) flush_end(b, stg, lane);
+    } else {
+      FLUSH(1);
+    }
     // adler32 trailer
     if (!uni(b.raw)) {
       uint32_t ad = A.adler[tr.stream];
@@ -3145,7 +3182,7 @@ struct TrialRun {
       }
       __syncthreads();
       if (wave != 0)
-        trial_flusher(A, s, mw, tr, (const GLOBAL uint32_t*)syms, (const GLOBAL uint8_t*)in, z.level, z.lbs, full_needed,
+        trial_flusher<FAM == 2>(A, s, mw, tr, (const GLOBAL uint32_t*)syms, (const GLOBAL uint8_t*)in, z.level, z.lbs, full_needed,
                       wave - 1, lane);
     }
     if constexpr (!MW) spec_init(s, A, tr, lane);   // (checked at each block flush: FLUSH0)
@@ -3241,6 +3278,29 @@ __global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_fast_gnu(SweepAr
 __global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_slow_gnu(SweepArgs A) {
   __shared__ TrialSharedSlow shm;
   trial_body<2, TrialSharedSlow, 0, 1>(A, shm, threadIdx.x);
+}
+// Flush-capable trials (Trial::host & TH_FLUSH; opt-in): the three default kinds and the two
+// multi-wave ones with FAM 2's end, which a trial's TM_FLUSH selects.  TM_RAW, never a saver, a replay or a
+// duplicate (ext_pass under the segment mask, deflate_dev).
+__global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_stored_flush(SweepArgs A) {
+  __shared__ struct { TrialShared t; uint64_t ring[(STAGE_WORDS + 1) / 2]; } shm;   // ring: staging only
+  trial_body<0, decltype(shm), 0, 2>(A, shm, threadIdx.x);
+}
+__global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_fast_flush(SweepArgs A) {
+  __shared__ TrialSharedFast<BITMAP_BITS> shm;
+  trial_body<1, TrialSharedFast<BITMAP_BITS>, 0, 2>(A, shm, threadIdx.x);
+}
+__global__ __launch_bounds__(64, TRIAL_SLOW_WAVES) void k_trial_slow_flush(SweepArgs A) {
+  __shared__ TrialSharedSlow shm;
+  trial_body<2, TrialSharedSlow, 0, 2>(A, shm, threadIdx.x);
+}
+__global__ __launch_bounds__(MW_THREADS, TRIAL_SLOW_WAVES) void k_trial_fast_flush_mw(SweepArgs A) {
+  __shared__ TrialSharedFastMW<BITMAP_BITS> shm;
+  trial_body<1, TrialSharedFastMW<BITMAP_BITS>, 0, 2>(A, shm, (int)(threadIdx.x & 63));
+}
+__global__ __launch_bounds__(MW_THREADS, TRIAL_SLOW_WAVES) void k_trial_slow_flush_mw(SweepArgs A) {
+  __shared__ TrialSharedSlowMW shm;
+  trial_body<2, TrialSharedSlowMW, 0, 2>(A, shm, (int)(threadIdx.x & 63));
 }
 
 }  // namespace atz

@@ -359,6 +359,64 @@ __global__ __launch_bounds__(256) void k_probe_ordered(const uint8_t* __restrict
   if (!write && t == 0) cnt[blockIdx.x] = total;
 }
 
+// The flush markers (the opt-in segment extension): the byte-aligned tail `00 00 FF FF` of the
+// empty stored block that a full flush writes.  k_headers_ordered's two passes once more: count mode writes
+// the block's total to cnt[b]; write mode writes the surviving positions q (q + 4 <= n) in file order from
+// base[b] on.  A lane owns the 16 positions of its 16-byte load and holds the 4 bytes after them too (3 are
+// needed); both loads stop at the file's end.
+__global__ __launch_bounds__(256) void k_marker_ordered(const uint8_t* __restrict__ f, uint64_t n, uint64_t seg,
+                                                        uint32_t* __restrict__ cnt, const uint64_t* __restrict__ base,
+                                                        uint64_t* __restrict__ out, int write) {
+  __shared__ uint32_t wsum[4];
+  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const uint64_t s0 = (uint64_t)blockIdx.x * seg;
+  const uint64_t s1 = s0 + seg < n ? s0 + seg : n;
+  uint64_t o = write ? base[blockIdx.x] : 0;
+  uint32_t total = 0;
+  for (uint64_t sb = s0; sb < s1; sb += 4096) {
+    const uint64_t p = sb + (uint64_t)t * 16;
+    uint32_t hits = 0;
+    if (p < s1) {
+      uint32_t d[5] = {0, 0, 0, 0, 0};
+      if (p + 20 <= n) {
+        const uint4 a = *reinterpret_cast<const uint4*>(f + p);
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
+        d[4] = *reinterpret_cast<const uint32_t*>(f + p + 16);
+      } else {
+        for (int k = 0; k < 20; k++)
+          if (p + k < n) d[k >> 2] |= (uint32_t)f[p + k] << (8 * (k & 3));
+      }
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        const uint32_t x = __funnelshift_r(d[k >> 2], d[(k >> 2) + 1], 8 * (k & 3));
+        hits |= (uint32_t)(x == 0xffff0000u && p + k < s1 && p + k + 4 <= n) << k;
+      }
+    }
+    const uint32_t c = __popc(hits);
+    uint32_t incl = c;
+    for (int e = 1; e < 64; e <<= 1) {
+      const uint32_t y = __shfl_up(incl, e, 64);
+      if ((int)lane >= e) incl += y;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint32_t before = 0, step = 0;
+    for (uint32_t k = 0; k < 4; k++) { const uint32_t y = wsum[k]; if (k < w) before += y; step += y; }
+    __syncthreads();
+    if (write) {
+      uint64_t q = o + before + incl - c;
+      while (hits) {
+        const int k = __ffs(hits) - 1;
+        hits &= hits - 1;
+        out[q++] = p + k;
+      }
+    }
+    o += step;
+    total += step;
+  }
+  if (!write && t == 0) cnt[blockIdx.x] = total;
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_inflate: one wavefront per job, everything inlined into the kernel so the decoder state stays
 // in (wave-uniform) SGPRs -- a by-reference state struct crossing a call would live in scratch.
@@ -449,7 +507,10 @@ struct InfShared {
 
 // RAW (the container extension's candidates): a raw deflate body -- no zlib header (HEAD)
 // and no Adler-32 trailer (CHECK); total_in is the position after the final block, rounded up to a byte.
-template <uint32_t RING, bool RAW = false>
+// SEG (the segment extension's jobs; only with RAW): one more stop -- the first stored block
+// with BFINAL = 0 and LEN = 0, a flush marker, ends the job as a final block does, with total_in the byte after
+// NLEN and INF_AT_MARKER in InfRes.err.
+template <uint32_t RING, bool RAW = false, bool SEG = false>
 __global__ __launch_bounds__(64, RING == INF_RING_FULL ? 1 : INF_SMALL_WAVES) void k_inflate(const uint8_t* __restrict__ in_base, uint8_t* __restrict__ out_base,
                                                const InfJob* __restrict__ jobs, InfRes* __restrict__ res,
                                                uint32_t njobs, uint8_t* __restrict__ arena,
@@ -916,6 +977,13 @@ __global__ __launch_bounds__(64, RING == INF_RING_FULL ? 1 : INF_SMALL_WAVES) vo
         if (len != (~nlen & 0xffff)) FAIL(5, pos + 32);
         drop(32);
         stage_flush();
+        if constexpr (SEG) {
+          if (!last && len == 0) {
+            flush(true);
+            hint |= INF_AT_MARKER;
+            return R_OK;
+          }
+        }
         // copy `len` bytes straight from the input (byte aligned now)
         const uint64_t avail = (limit - pos) >> 3;
         const uint64_t take = len < avail ? len : avail;

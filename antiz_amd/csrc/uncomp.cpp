@@ -399,8 +399,9 @@ int main(int argc, char* argv[]) {
     }
     // ("ATZ\2": a file of the strategy extension, ATZ_STRATEGIES below; "ATZ\3": of the container extension,
     // ATZ_CONTAINERS; same layout; "ATZ\4": of the stitch extension, ATZ_STITCH, whose stitched descriptors carry a
-    // piece list; "ATZ\5": of the deflater extension, ATZ_DEFLATERS, version 4's layout)
-    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 5) {
+    // piece list; "ATZ\5": of the deflater extension, ATZ_DEFLATERS, version 4's layout; "ATZ\6": of the segment
+    // extension, ATZ_SEGMENTS, likewise)
+    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 6) {
       std::cout << "Invalid file: ATZ1 header not found" << std::endl;
       return -2;
     }
@@ -513,7 +514,23 @@ int main(int argc, char* argv[]) {
       }
     }
   }
+  // ATZ_SEGMENTS=flush (not a reference flag): streams cut by full-flush points are recorded segment by segment
+  // (atz_set_segments)
+  uint32_t segments = 0;
+  if (const char* e = std::getenv("ATZ_SEGMENTS")) {
+    std::stringstream words(e);
+    std::string w;
+    while (std::getline(words, w, ',')) {
+      if (w.empty()) continue;
+      if (w == "flush") segments |= 1u << 0;
+      else {
+        std::cerr << "Error Encountered: " << "ATZ_SEGMENTS: unknown segment kind " << w << std::endl;
+        return done(1);
+      }
+    }
+  }
   if (open_ctx()) return done(255);
+  if (segments && atz_set_segments(ctx, segments) != 0) return done(255);
   if (deflaters && atz_set_deflaters(ctx, deflaters) != 0) return done(255);
   if (strategies && atz_set_strategies(ctx, strategies) != 0) return done(255);
   if (containers && atz_set_containers(ctx, containers) != 0) return done(255);

@@ -17,11 +17,12 @@
  *   atz_deflate     one deflateInit2/deflate(Z_FINISH)/deflateEnd              main.cpp:976-1003
  *   atz_shard_*     the precompress of one file split over several GPUs (new: the reference is
  *                   single-threaded)
- * Five opt-in extensions, each off by default and leaving every output as the reference's while off:
+ * Six opt-in extensions, each off by default and leaving every output as the reference's while off:
  *   atz_set_strategies  zlib strategy trials ("ATZ\2"), atz_set_containers  raw deflate in ZIP / gzip ("ATZ\3"),
  *   atz_set_stitch      zlib streams split over PNG IDAT chunks ("ATZ\4"),
  *   atz_set_probe       raw deflate streams that nothing announces ("ATZ\3"),
- *   atz_set_deflaters   raw bodies written by GNU gzip's and Info-ZIP's deflater, not zlib's ("ATZ\5")
+ *   atz_set_deflaters   raw bodies written by GNU gzip's and Info-ZIP's deflater, not zlib's ("ATZ\5"),
+ *   atz_set_segments    streams cut by full-flush points, one raw record per segment ("ATZ\6")
  */
 #ifndef ATZ_ACCEL_H
 #define ATZ_ACCEL_H
@@ -60,7 +61,9 @@ typedef struct {
                             more blocks follow, else 0 (a sweep hint, likewise not the reference's); bit 6: a
                             stitched record (only with atz_set_stitch): a zlib stream split over k >= 2 PNG IDAT
                             chunks -- offset is its first payload byte, comp_len its length in stream bytes, and
-                            it occupies [offset, offset + comp_len + 12 (k - 1)) of the file (atz_stitch_pieces) */
+                            it occupies [offset, offset + comp_len + 12 (k - 1)) of the file (atz_stitch_pieces);
+                            bit 7: a flush-terminated segment (only with atz_set_segments): a raw record (type
+                            24-26) that ends with a full flush's empty stored block, not with a final block */
 } atz_cand_t;
 
 /* ATZdata::streamOffset after Phase 3. */
@@ -244,11 +247,46 @@ int atz_probe_positions(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint6
  * gets nine more candidates, levels 1-9 in the hint's order, directly behind the memLevel-8 group (positions
  * 10-18 of 99).  A body recorded so reports clevel = 1<<6 | level, window 15 and memLevel 0, and a file that
  * holds one is written with the magic "ATZ\5" (version 4's layout; memLevel byte 0 only on such a descriptor),
- * else the file is what a context without this mask writes.  atz_reconstruct* read all five.  In
+ * else the file is what a context without this mask writes.  atz_reconstruct* read every version.  In
  * atz_deflate_batch_ex, bit 29 of a params word asks for this deflater: only with bit 28, window 15, strategy
  * 0 and level 1-9 (else ATZ_E_ARG); the memLevel field is ignored.  The atz_shard_* calls return ATZ_E_ARG on
  * a context with a mask. */
 int atz_set_deflaters(atz_ctx_t *ctx, uint32_t mask);
+
+/* Opt-in segments (an extension: a stream cut by full-flush points -- deflate(.., Z_FULL_FLUSH), pigz -i,
+ * dictzip-style seekable gzip -- is recorded by no one-shot deflate).  mask bit 0: "flush"; 0, the default, is off
+ * and leaves every output as what a context without this mask writes.  After a full flush zlib starts from a
+ * fresh state, so such a stream is a chain of independent raw bodies, each the one-shot deflate of its bytes but
+ * for its end: no block is final, an empty last block is absent, and three zero bits, padding to a byte and
+ * 00 00 FF FF follow.  With the mask, the scan lists every position q with bytes q..q+3 = 00 00 FF FF; a record
+ * is eligible if it is raw (type 24-26; body = the record) or a zlib record whose header says window 15 and that
+ * is not stitched (body = the record without its 2 header and 4 trailer bytes), and holds a marker with
+ * body_start <= q and q + 4 < body_end.  The body's start and every such q + 4 are decoded as raw streams that
+ * also end at the first stored block with BFINAL = 0 and LEN = 0.  The chain s_0 = body_start, s_(i+1) = s_i +
+ * consumed_i over decodes that ended at such a block with output completes when it reaches one that ended at a
+ * final block exactly at body_end, after at least one marker, with the outputs summing to the record's infl_len.
+ * Then the record is replaced, in file order, by its segments {s_i, consumed_i, produced_i} of type 24 + hint (a
+ * raw parent's; a zlib parent's FLEVEL 0 and 1 give 25, 2 gives 24, 3 gives 26), every one but the last with
+ * atz_cand_t.flags bit 7; a last segment without output makes no record; a zlib parent's header and trailer
+ * become residue.  Any other record stays exactly as it is.  Segments are walked as raw records are (window 15,
+ * the default strategy; a bit-7 segment's trials end as a full flush does, and it gets no GNU candidates).  A
+ * recorded bit-7 segment reports clevel = 1<<6 | level and window 0x8F, and a file that holds one is written with
+ * the magic "ATZ\6" (version 5's layout; window byte 0x8F only on such a descriptor), else the file is what a
+ * context without this mask writes.  atz_reconstruct* read all six.  In atz_deflate_batch_ex, bit 30 of a params
+ * word asks for a flush-terminated body: only with bit 28, without bit 29, strategy 0 and windows 9-15 (else
+ * ATZ_E_ARG).  The atz_shard_* calls return ATZ_E_ARG on a context with a mask. */
+int atz_set_segments(atz_ctx_t *ctx, uint32_t mask);
+
+/* The marker kernel's list for a host buffer (parity/debug): *out (atz_free) receives the *n positions q with
+ * q + 4 <= len and bytes q..q+3 = 00 00 FF FF, ascending. */
+int atz_flush_markers(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint64_t **out, uint64_t *n);
+
+/* atz_inflate_batch on raw deflate bodies (no zlib header, no trailer) with the segment decoder (parity/debug):
+ * a job also ends, with status 0, at the first stored block with BFINAL = 0 and LEN = 0 -- consumed[i] is then
+ * the byte after NLEN and at_marker[i] = 1; at a final block at_marker[i] = 0. */
+int atz_inflate_segments(atz_ctx_t *ctx, const uint8_t *buf, uint64_t len, const uint64_t *offs,
+                         const uint64_t *lens, uint64_t n, uint32_t *status, uint64_t *consumed,
+                         uint64_t *produced, uint8_t *at_marker);
 
 /* Batch of independent one-shot inflates of the given ranges of a host buffer (parity/debug):
  * status[i] in {0 end, 1 error, 2 need input}, consumed[i] = zlib total_in, produced[i] = total_out. */
