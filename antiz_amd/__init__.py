@@ -63,16 +63,21 @@ EXPORTS = ["atz_open", "atz_close", "atz_strerror", "atz_free", "atz_default_opt
 STRATEGIES = {"filtered": 1, "huffman": 2, "rle": 3}
 
 
-def strategy_mask(names):
-    """("filtered", "rle", ...) or a comma-separated string -> atz_set_strategies mask; ValueError on an unknown word."""
+def _mask(names, table, noun):
+    """Words (a sequence, or a comma-separated string) -> the mask with bit table[w] set for each; ValueError on an unknown word."""
     if isinstance(names, str):
         names = [w for w in names.split(",") if w]
     mask = 0
     for w in names:
-        if w not in STRATEGIES:
-            raise ValueError("unknown strategy %r (known: %s)" % (w, ", ".join(sorted(STRATEGIES))))
-        mask |= 1 << STRATEGIES[w]
+        if w not in table:
+            raise ValueError("unknown %s %r (known: %s)" % (noun, w, ", ".join(sorted(table))))
+        mask |= 1 << table[w]
     return mask
+
+
+def strategy_mask(names):
+    """("filtered", "rle", ...) or a comma-separated string -> atz_set_strategies mask; ValueError on an unknown word."""
+    return _mask(names, STRATEGIES, "strategy")
 
 
 # containers whose raw deflate bodies a container mask makes the scan look for: bit number of each
@@ -81,14 +86,7 @@ CONTAINERS = {"zip": 0, "gzip": 1}
 
 def container_mask(names):
     """("zip", "gzip") or a comma-separated string -> atz_set_containers mask; ValueError on an unknown word."""
-    if isinstance(names, str):
-        names = [w for w in names.split(",") if w]
-    mask = 0
-    for w in names:
-        if w not in CONTAINERS:
-            raise ValueError("unknown container %r (known: %s)" % (w, ", ".join(sorted(CONTAINERS))))
-        mask |= 1 << CONTAINERS[w]
-    return mask
+    return _mask(names, CONTAINERS, "container")
 
 
 # what a stitch mask makes the scan put together: bit number of each
@@ -97,14 +95,7 @@ STITCHERS = {"png": 0}
 
 def stitch_mask(names):
     """("png",) or a comma-separated string -> atz_set_stitch mask; ValueError on an unknown word."""
-    if isinstance(names, str):
-        names = [w for w in names.split(",") if w]
-    mask = 0
-    for w in names:
-        if w not in STITCHERS:
-            raise ValueError("unknown stitcher %r (known: %s)" % (w, ", ".join(sorted(STITCHERS))))
-        mask |= 1 << STITCHERS[w]
-    return mask
+    return _mask(names, STITCHERS, "stitcher")
 
 
 # what a probe mask makes the scan test every byte position for: bit number of each
@@ -113,14 +104,7 @@ PROBES = {"deflate": 0}
 
 def probe_mask(names):
     """("deflate",) or a comma-separated string -> atz_set_probe mask; ValueError on an unknown word."""
-    if isinstance(names, str):
-        names = [w for w in names.split(",") if w]
-    mask = 0
-    for w in names:
-        if w not in PROBES:
-            raise ValueError("unknown probe %r (known: %s)" % (w, ", ".join(sorted(PROBES))))
-        mask |= 1 << PROBES[w]
-    return mask
+    return _mask(names, PROBES, "probe")
 
 
 # deflater families beside zlib's that a deflater mask adds to the raw walk: bit number of each
@@ -129,14 +113,7 @@ DEFLATERS = {"gnu": 0}
 
 def deflater_mask(names):
     """("gnu",) or a comma-separated string -> atz_set_deflaters mask; ValueError on an unknown word."""
-    if isinstance(names, str):
-        names = [w for w in names.split(",") if w]
-    mask = 0
-    for w in names:
-        if w not in DEFLATERS:
-            raise ValueError("unknown deflater %r (known: %s)" % (w, ", ".join(sorted(DEFLATERS))))
-        mask |= 1 << DEFLATERS[w]
-    return mask
+    return _mask(names, DEFLATERS, "deflater")
 
 
 # what a segments mask makes the scan split streams at: bit number of each
@@ -145,44 +122,46 @@ SEGMENTS = {"flush": 0}
 
 def segments_mask(names):
     """("flush",) or a comma-separated string -> atz_set_segments mask; ValueError on an unknown word."""
-    if isinstance(names, str):
-        names = [w for w in names.split(",") if w]
-    mask = 0
-    for w in names:
-        if w not in SEGMENTS:
-            raise ValueError("unknown segment kind %r (known: %s)" % (w, ", ".join(sorted(SEGMENTS))))
-        mask |= 1 << SEGMENTS[w]
-    return mask
+    return _mask(names, SEGMENTS, "segment kind")
+
+
+# The clevel byte of a descriptor: stitched << 7 | raw << 6 | strategy << 4 | level (csrc/atz_params.h).
+def _pack(strategy, level, raw, stitched):
+    if raw and stitched:
+        raise ValueError("a descriptor is raw or stitched, not both")
+    if not (0 <= strategy <= 3 and 0 <= level <= 9) or (strategy >= 2 and level < 1):
+        raise ValueError("strategy %d with level %d" % (strategy, level))
+    return (int(bool(stitched)) << 7) | (int(bool(raw)) << 6) | (strategy << 4) | level
+
+
+def _unpack(b):
+    return bool(b & 0x80), bool(b & 0x40), (b >> 4) & 3, b & 15
 
 
 def pack_clevel(strategy, level, raw=False):
     """The clevel byte of an ATZ2 / ATZ3 descriptor (and of atz_sweep's results): raw << 6 | strategy << 4 | level."""
-    if not (0 <= strategy <= 3 and 0 <= level <= 9) or (strategy >= 2 and level < 1):
-        raise ValueError("strategy %d with level %d" % (strategy, level))
-    return (int(bool(raw)) << 6) | (strategy << 4) | level
+    return _pack(strategy, level, raw, False)
 
 
 def unpack_clevel(b):
     """-> (strategy, level) of a clevel byte."""
-    return b >> 4, b & 15
+    return b >> 4, _unpack(b)[3]
 
 
 def unpack_clevel3(b):
     """-> (raw, strategy, level) of an ATZ3 clevel byte."""
-    return bool(b & 0x40), (b >> 4) & 3, b & 15
-
+    return _unpack(b)[1:]
 
 
 def pack_clevel4(strategy, level, raw=False, stitched=False):
     """The clevel byte of an ATZ4 descriptor: stitched << 7 | raw << 6 | strategy << 4 | level (never both)."""
-    if raw and stitched:
-        raise ValueError("a descriptor is raw or stitched, not both")
-    return (int(bool(stitched)) << 7) | pack_clevel(strategy, level, raw)
+    return _pack(strategy, level, raw, stitched)
 
 
 def unpack_clevel4(b):
     """-> (stitched, raw, strategy, level) of an ATZ4 clevel byte."""
-    return (bool(b & 0x80),) + unpack_clevel3(b & 0x7f)
+    return _unpack(b)
+
 
 _lib = None
 

@@ -42,6 +42,7 @@
 #include <ucontext.h>
 
 #include "../../include/atz_accel.h"
+#include "atz_params.h"
 
 using namespace atz;
 
@@ -389,47 +390,6 @@ struct StreamState {
   std::vector<std::array<uint16_t, 5>> xl;   // {window, memLevel, level, imp, len}
 };
 
-
-uint32_t pk(int c, int w, int m) { return ((uint32_t)c << 16) | ((uint32_t)w << 8) | (uint32_t)m; }
-
-void prange(std::vector<uint32_t>& l, int cmin, int cmax, int wmin, int wmax, int mmin, int mmax) {
-  for (int w = wmax; w >= wmin; w--)
-    for (int m = mmax; m >= mmin; m--)
-      for (int c = cmax; c >= cmin; c--) l.push_back(pk(c, w, m));
-}
-// tryParamsFastest/Fast/Default/Best (main.cpp:487-560)
-void list_a(std::vector<uint32_t>& l, int type) {
-  if (type >= 24) return;   // a raw record (the container extension): the reference walk leaves it alone
-  int w = 10 + type / 4;
-  switch (type % 4) {
-    case 0: l.push_back(pk(0, w, 8)); l.push_back(pk(1, w, 8)); l.push_back(pk(1, w, 9));
-            prange(l, 1, 1, w, w, 1, 7); prange(l, 2, 9, w, w, 1, 9); break;
-    case 1: prange(l, 2, 5, w, w, 8, 8); prange(l, 2, 5, w, w, 1, 7); prange(l, 2, 5, w, w, 9, 9);
-            prange(l, 1, 1, w, w, 1, 9); prange(l, 6, 9, w, w, 1, 9); break;
-    case 2: l.push_back(pk(6, w, 8)); l.push_back(pk(6, w, 9)); prange(l, 6, 6, w, w, 1, 7);
-            prange(l, 1, 5, w, w, 1, 9); prange(l, 7, 9, w, w, 1, 9); break;
-    default: prange(l, 7, 9, w, w, 8, 8); prange(l, 7, 9, w, w, 1, 7); prange(l, 7, 9, w, w, 9, 9);
-             prange(l, 1, 6, w, w, 1, 9); break;
-  }
-}
-// brute-window continuation (main.cpp:590-601)
-void list_b(std::vector<uint32_t>& l, int type) {
-  if (type >= 24) return;
-  int w = 10 + type / 4;
-  if (w == 10) prange(l, 1, 9, 11, 15, 1, 9);
-  else if (w == 15) prange(l, 1, 9, 10, 14, 1, 9);
-  else { prange(l, 1, 9, 10, w - 1, 1, 9); prange(l, 1, 9, w + 1, 15, 1, 9); }
-}
-
-// The trial lists depend only on the header type (24) and the phase: built once, shared by streams.
-const std::vector<uint32_t>& trial_list(int type, bool brute) {
-  static const std::array<std::array<std::vector<uint32_t>, 27>, 2> L = [] {   // 24..26: raw records, empty
-    std::array<std::array<std::vector<uint32_t>, 27>, 2> t;
-    for (int ty = 0; ty < 27; ty++) { list_a(t[0][ty], ty); list_b(t[1][ty], ty); }
-    return t;
-  }();
-  return L[brute ? 1 : 0][type];
-}
 
 uint64_t bound(uint64_t n, int w, int m) {  // deflateBound (Z/deflate.c:566-621), zlib wrapper
   uint64_t complen = n + ((n + 7) >> 3) + ((n + 63) >> 6) + 5;
@@ -1429,6 +1389,18 @@ static int ordered_list_dev(atz_ctx* c, uint64_t F, const char* name, Launch lau
   return 0;
 }
 
+// the positions an ordered list kernel without further arguments finds in the file (ProbeList, MarkerList)
+template <class Kernel, class List>
+static int positions_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, Kernel kernel, const char* name, List& L) {
+  L.pos.clear();
+  L.kernel_ms = 0;
+  if (!F) return 0;
+  auto launch = [&](uint32_t nb, uint64_t seg, uint32_t* cnt, const uint64_t* base, uint64_t* dst, int write) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, c->st, d_file, F, seg, cnt, base, dst, write);
+  };
+  return ordered_list_dev(c, F, name, launch, L.pos, &L.kernel_ms);
+}
+
 // the anchors of the file, ascending: position << 5 | kind
 static int anchors_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint32_t mask, std::vector<uint64_t>& out) {
   out.clear();
@@ -1495,6 +1467,31 @@ static void raw_candidates(const uint8_t* h, uint64_t n, const std::vector<uint6
   }
 }
 
+// A record of ref (in file order, disjoint) meets the file range [lo, hi): only the last one that starts below
+// hi can.  (raw_merge used to compare comp_len, not hull(): no stitched record exists when it runs, so the
+// two are equal there.)
+static bool meets_earlier(const std::vector<Rec>& ref, uint64_t lo, uint64_t hi) {
+  const auto it = std::lower_bound(ref.begin(), ref.end(), hi, [](const Rec& x, uint64_t v) { return x.offset < v; });
+  return it != ref.begin() && (it - 1)->offset + (it - 1)->hull() > lo;
+}
+// The new records (ascending offsets, disjoint, meeting no record of c->recs) take their places in c->recs, which
+// keeps its capacity (the sweep's tables are sized for it).
+static int splice_records(atz_ctx* c, const std::vector<Rec>& add) {
+  if (add.empty()) return 0;
+  const std::vector<Rec>& ref = c->recs;
+  std::vector<Rec> merged;
+  merged.reserve(ref.size() + add.size());
+  size_t i = 0;
+  for (const Rec& e : add) {
+    while (i < ref.size() && ref[i].offset < e.offset) merged.push_back(ref[i++]);
+    merged.push_back(e);
+  }
+  while (i < ref.size()) merged.push_back(ref[i++]);
+  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
+  c->recs.assign(merged.begin(), merged.end());
+  return 0;
+}
+
 // The raw records of the file merged into c->recs (the reference's, complete): candidates decoded (outputs
 // kept in the scan's arena, behind the reference candidates'; fresh_arena: the scan ran no job), accepted
 // by the container's own fields, dropped where they meet a reference record, taken greedily in ascending
@@ -1508,7 +1505,6 @@ static int raw_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64
   std::vector<InfRes> res;
   if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, arena_cap, false, fresh_arena, true)) return r;
   std::vector<std::pair<Rec, uint64_t>> acc;   // (record, anchor position)
-  const std::vector<Rec>& ref = c->recs;
   for (size_t k = 0; k < cands.size(); k++) {
     const RawCand& a = cands[k];
     const InfRes& r = res[k];
@@ -1520,28 +1516,21 @@ static int raw_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64
       continue;
     }
     // a reference record that meets [d, d + consumed): the raw one is dropped
-    const uint64_t lo = a.d, hi = a.d + r.consumed;
-    const auto it = std::lower_bound(ref.begin(), ref.end(), hi, [](const Rec& x, uint64_t v) { return x.offset < v; });
-    if (it != ref.begin() && (it - 1)->offset + (it - 1)->comp_len > lo) continue;
+    if (meets_earlier(c->recs, a.d, a.d + r.consumed)) continue;
     Rec rec{a.d, r.consumed, r.produced, 24 + a.hint, 0, r.arena_off};
     acc.push_back({rec, a.p});
   }
   std::stable_sort(acc.begin(), acc.end(), [](const auto& x, const auto& y) {
     return x.first.offset != y.first.offset ? x.first.offset < y.first.offset : x.second < y.second;
   });
-  std::vector<Rec> merged;
-  merged.reserve(ref.size() + acc.size());
-  size_t i = 0;
+  std::vector<Rec> kept;
   uint64_t end = 0;
   for (const auto& e : acc) {
     if (e.first.offset < end) continue;   // starts inside the raw record kept before it
     end = e.first.offset + e.first.comp_len;
-    while (i < ref.size() && ref[i].offset < e.first.offset) merged.push_back(ref[i++]);
-    merged.push_back(e.first);
+    kept.push_back(e.first);
   }
-  while (i < ref.size()) merged.push_back(ref[i++]);
-  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
-  c->recs.assign(merged.begin(), merged.end());
+  if (int r = splice_records(c, kept)) return r;
   TMARK("scan: raw candidates");
   return 0;
 }
@@ -1644,8 +1633,7 @@ static int stitch_merge(atz_ctx* c, const uint8_t* d_file, uint64_t arena_cap, b
     std::fprintf(stderr, "atz: stitch: %zu candidates, %llu bytes in %zu segments, k_gather %.3f ms, k_inflate %.3f ms\n",
                  P.cands.size(), (unsigned long long)P.bytes, segs.size(), c->stats.k_other_ms - other0,
                  c->stats.k_inflate_ms - infl0);
-  const std::vector<Rec>& ref = c->recs;
-  std::vector<Rec> acc;
+  std::vector<Rec> acc;   // (the candidates are in file order and disjoint, as their chains are)
   for (size_t k = 0; k < P.cands.size(); k++) {
     const StitchCand& a = P.cands[k];
     const InfRes& r = res[k];
@@ -1666,24 +1654,13 @@ static int stitch_merge(atz_ctx* c, const uint8_t* d_file, uint64_t arena_cap, b
     }
     if (sum != r.consumed) return ATZ_E_INTERNAL;   // (the decoder never reads past the run)
     // a record made before that meets the hull [offset, offset + hull): the stitched one is dropped
-    const uint64_t lo = rec.offset, hi = rec.offset + rec.hull();
-    const auto it = std::lower_bound(ref.begin(), ref.end(), hi, [](const Rec& x, uint64_t v) { return x.offset < v; });
-    if (it != ref.begin() && (it - 1)->offset + (it - 1)->hull() > lo) {
+    if (meets_earlier(c->recs, rec.offset, rec.offset + rec.hull())) {
       c->st_off.resize(rec.p0); c->st_len.resize(rec.p0);
       continue;
     }
     acc.push_back(rec);
   }
-  std::vector<Rec> merged;   // (the candidates are in file order and disjoint, as their chains are)
-  merged.reserve(ref.size() + acc.size());
-  size_t i = 0;
-  for (const Rec& e : acc) {
-    while (i < ref.size() && ref[i].offset < e.offset) merged.push_back(ref[i++]);
-    merged.push_back(e);
-  }
-  while (i < ref.size()) merged.push_back(ref[i++]);
-  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
-  c->recs.assign(merged.begin(), merged.end());
+  if (int r = splice_records(c, acc)) return r;
   TMARK("scan: stitched candidates");
   return 0;
 }
@@ -1696,13 +1673,7 @@ static int stitch_merge(atz_ctx* c, const uint8_t* d_file, uint64_t arena_cap, b
 // which raw_pass walks as it walks a container's body.
 static constexpr uint64_t PROBE_MIN_OUT = 256;   // a dynamic header alone is 40-80 bytes: smaller bodies gain nothing
 static int probe_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, ProbeList& P) {
-  P.pos.clear();
-  P.kernel_ms = 0;
-  if (!F) return 0;
-  auto launch = [&](uint32_t nb, uint64_t seg, uint32_t* cnt, const uint64_t* base, uint64_t* dst, int write) {
-    hipLaunchKernelGGL(k_probe_ordered, dim3(nb), dim3(256), 0, c->st, d_file, F, seg, cnt, base, dst, write);
-  };
-  return ordered_list_dev(c, F, "k_probe_ordered", launch, P.pos, &P.kernel_ms);
+  return positions_dev(c, d_file, F, k_probe_ordered, "k_probe_ordered", P);
 }
 
 // The probe's records merged into c->recs (every record made before, complete, in file order): survivors
@@ -1726,30 +1697,24 @@ static int probe_merge(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint64_t a
   const double infl0 = c->stats.k_inflate_ms;
   std::vector<InfRes> res;
   if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, arena_cap, false, fresh_arena, true)) return r;
-  std::vector<Rec> merged;
-  merged.reserve(ref.size() + 16);
-  size_t i = 0, accepted = 0, kept = 0;
+  std::vector<Rec> kept;
+  size_t accepted = 0;
   uint64_t end = 0;
   for (size_t k = 0; k < jobs.size(); k++) {
     const InfRes& r = res[k];
     if (r.status != INF_END || r.produced < PROBE_MIN_OUT || r.produced >= (1ull << 31)) continue;
     accepted++;
     const uint64_t lo = jobs[k].in_off, hi = lo + r.consumed;
-    const auto it = std::lower_bound(ref.begin(), ref.end(), hi, [](const Rec& x, uint64_t v) { return x.offset < v; });
-    if (it != ref.begin() && (it - 1)->offset + (it - 1)->hull() > lo) continue;
+    if (meets_earlier(ref, lo, hi)) continue;
     if (lo < end) continue;   // starts inside the probe record kept before it
     end = hi;
-    while (i < ref.size() && ref[i].offset < lo) merged.push_back(ref[i++]);
-    merged.push_back(Rec{lo, r.consumed, r.produced, 24 /* raw, hint none */, 0, r.arena_off});
-    kept++;
+    kept.push_back(Rec{lo, r.consumed, r.produced, 24 /* raw, hint none */, 0, r.arena_off});
   }
-  while (i < ref.size()) merged.push_back(ref[i++]);
   if (timing_on())
     std::fprintf(stderr, "atz: k_probe_ordered: %zu survivors, kernels %.3f ms (both passes), %zu decoded, "
                  "k_inflate %.3f ms, %zu accepted, %zu kept\n", P.pos.size(), P.kernel_ms, jobs.size(),
-                 c->stats.k_inflate_ms - infl0, accepted, kept);
-  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
-  if (kept) c->recs.assign(merged.begin(), merged.end());
+                 c->stats.k_inflate_ms - infl0, accepted, kept.size());
+  if (int r = splice_records(c, kept)) return r;
   TMARK("scan: probe candidates");
   return 0;
 }
@@ -1762,13 +1727,7 @@ static int probe_merge(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint64_t a
 // start of the eligible records in one launch of k_inflate's SEG variant and replaces a record whose chain
 // completes by its segments.
 static int markers_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, MarkerList& M) {
-  M.pos.clear();
-  M.kernel_ms = 0;
-  if (!F) return 0;
-  auto launch = [&](uint32_t nb, uint64_t seg, uint32_t* cnt, const uint64_t* base, uint64_t* dst, int write) {
-    hipLaunchKernelGGL(k_marker_ordered, dim3(nb), dim3(256), 0, c->st, d_file, F, seg, cnt, base, dst, write);
-  };
-  return ordered_list_dev(c, F, "k_marker_ordered", launch, M.pos, &M.kernel_ms);
+  return positions_dev(c, d_file, F, k_marker_ordered, "k_marker_ordered", M);
 }
 
 // Eligible: a raw record (type 24-26; its body is the record), or a zlib record whose header says window 15 and
@@ -1872,35 +1831,63 @@ static uint64_t rec_src(const atz_ctx* c, const Rec& r, const uint8_t* d_file) {
   return r.stitch == ~0ull ? r.offset : (uint64_t)(uintptr_t)c->d_stitch.p + r.stitch - (uint64_t)(uintptr_t)d_file;
 }
 
+// The scan's opt-in extensions (container, stitch, probe, segment): what ext_prepare lists before the scan for
+// ext_merge to turn into records after it.  Every list is empty without its mask.
+struct ScanExt {
+  std::vector<RawCand> raw;
+  StitchPlan stitch;
+  ProbeList& probe;    // the context's (their storage is reused from call to call)
+  MarkerList& marks;
+  explicit ScanExt(atz_ctx* c) : probe(c->probe), marks(c->marks) {}
+  // the records ext_merge can add: the sweep's tables have room for them (a marker adds one at the most)
+  size_t extra_records() const { return raw.size() + stitch.cands.size() + probe.pos.size() + marks.pos.size(); }
+};
+static bool ext_on(const atz_ctx* c) { return ext_anchor_mask(c) || c->probe_mask || c->seg_mask; }
+
+// the list kernels and the host parsers of the masks that are on
+static int ext_prepare(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t F, ScanExt& E) {
+  E.raw.clear(); E.stitch = StitchPlan{}; E.probe.pos.clear(); E.marks.pos.clear();
+  c->st_off.clear(); c->st_len.clear();
+  std::vector<uint64_t> anchors;
+  if (int r = anchors_dev(c, d_file, F, ext_anchor_mask(c), anchors)) return r;   // (no mask: no anchor)
+  raw_candidates(h, F, anchors, E.raw);
+  stitch_candidates(h, anchors, E.stitch);
+  if (c->probe_mask)
+    if (int r = probe_dev(c, d_file, F, E.probe)) return r;
+  if (c->seg_mask)
+    if (int r = markers_dev(c, d_file, F, E.marks)) return r;
+  return 0;
+}
+
+// The extensions' records merged into c->recs (the reference's, complete), each step seeing the records of the
+// steps before it.  The decoded outputs go to the scan's arena, which is fresh for a step while no job ran
+// before it: none of the scan's own (S.fjobs) and none of an earlier step's.  A step with candidates runs its
+// jobs whether it accepts one or not, so its non-empty candidate list clears the flag.  (probe_merge goes through
+// run_inflate_jobs even with no job.)
+static int ext_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t F, const ScanState& S, const ScanExt& E) {
+  bool fresh = S.fjobs.empty();
+  if (int r = raw_merge(c, h, d_file, S.arena_cap, fresh, E.raw)) return r;
+  fresh = fresh && E.raw.empty();
+  if (int r = stitch_merge(c, d_file, S.arena_cap, fresh, E.stitch)) return r;
+  fresh = fresh && E.stitch.cands.empty();
+  if (c->probe_mask)
+    if (int r = probe_merge(c, d_file, F, S.arena_cap, fresh, E.probe)) return r;
+  if (c->seg_mask)
+    if (int r = seg_merge(c, h, d_file, E.marks)) return r;
+  return 0;
+}
+
 // Every record, one piece.  (atz_scan; precompress_dev scans piece by piece while the sweep runs)
 static int scan_impl(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t F) {
   auto t0 = std::chrono::steady_clock::now();
   c->recs.clear();
   ScanState S;
   if (int r = scan_plan(c, h, d_file, F, S)) return r;
-  std::vector<uint64_t> anchors;
-  std::vector<RawCand> rc;
-  StitchPlan sp;
-  if (int r = anchors_dev(c, d_file, F, ext_anchor_mask(c), anchors)) return r;
-  raw_candidates(h, F, anchors, rc);
-  stitch_candidates(h, anchors, sp);
-  ProbeList& pl = c->probe;
-  pl.pos.clear();
-  if (c->probe_mask)
-    if (int r = probe_dev(c, d_file, F, pl)) return r;
-  MarkerList& ml = c->marks;
-  ml.pos.clear();
-  if (c->seg_mask)   // (one more record per marker at the most)
-    if (int r = markers_dev(c, d_file, F, ml)) return r;
-  c->st_off.clear(); c->st_len.clear();
-  c->recs.reserve(S.max_records() + rc.size() + sp.cands.size() + pl.pos.size() + ml.pos.size());
+  ScanExt E(c);
+  if (int r = ext_prepare(c, h, d_file, F, E)) return r;
+  c->recs.reserve(S.max_records() + E.extra_records());
   if (int r = scan_piece(c, h, d_file, S, 0, (uint32_t)S.chunks.size())) return r;
-  if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), rc)) return r;
-  if (int r = stitch_merge(c, d_file, S.arena_cap, S.fjobs.empty() && rc.empty(), sp)) return r;
-  if (c->probe_mask)
-    if (int r = probe_merge(c, d_file, F, S.arena_cap, S.fjobs.empty() && rc.empty() && sp.cands.empty(), pl)) return r;
-  if (c->seg_mask)
-    if (int r = seg_merge(c, h, d_file, ml)) return r;
+  if (int r = ext_merge(c, h, d_file, F, S, E)) return r;
   c->stats.scan_ms = ms_since(t0);
   return 0;
 }
@@ -2411,11 +2398,14 @@ static uint32_t trial_variant(const Pipe* c, int k, const Trial& t) {
   if (t.host & TH_FLUSH) return 16u | (mw_trial(c, k, t.memlevel) ? 1u : 0u);
   return (mw_trial(c, k, t.memlevel) ? 1u : 0u) | ((t.host & TH_STRAT) << 1);
 }
-// (memlevel 0: a GNU-family trial, whose blocks hold up to 32 767 symbols whatever the stream's tables)
-static uint64_t sym_words(const Pipe* c, int kind, uint32_t memlevel, uint64_t n) {   // symbol buffer of a trial (u32 units)
-  if (!memlevel) return 32768 + 64;
-  return (mw_trial(c, kind, memlevel) ? n + 64 : 0) + (1ull << (memlevel + 6)) + 64;
+// (a GNU-family trial's blocks hold up to 32 767 symbols whatever the stream's tables)
+static uint64_t sym_words(const Pipe* c, int kind, const DeflSpec& p, uint64_t n) {   // symbol buffer of a trial (u32 units)
+  if (p.gnu) return 32768 + 64;
+  return (mw_trial(c, kind, (uint32_t)p.memlevel) ? n + 64 : 0) + (1ull << (p.memlevel + 6)) + 64;
 }
+// (deflateBound reads the memLevel a GNU-family trial does not have: it takes the general bound)
+static uint64_t bound(uint64_t n, const DeflSpec& p) { return bound(n, p.window, p.gnu ? 0 : p.memlevel); }
+static_assert(TM_RAW == 2 && TM_FLUSH == 64, "DeflSpec::mode() writes these bits");
 // The trials of one batch on a pipe, by kind (0 stored, 1 fast, 2 slow levels), each with its slice of the
 // pipe's output and symbol scratch.  Every trial descriptor is made here (Round, strategy_pass, deflate_dev).
 struct TrialBatch {
@@ -2424,23 +2414,24 @@ struct TrialBatch {
   // the raw pass of a context with the segment mask: every default-strategy zlib trial goes to the flush-capable
   // kernels (TH_FLUSH), so that a list step's flush-terminated and finished trials share their launches
   bool flush_kernels = false;
-  // A trial of stream s (len inflated bytes) at (level, window, memLevel) under zlib strategy strat.
+  // A trial of stream s (len inflated bytes) with the parameters p and the mode bits p does not give (TM_FULL).
   // Z_RLE and Z_HUFFMAN_ONLY ignore the level and read no tables (the stored kind's kernels); Z_FILTERED
-  // only changes deflate_slow, so on levels 1-3 it is the default strategy.  m == 0: a GNU-family trial (level
-  // 1-9, raw, default strategy: the callers' checks), which parses at memLevel 8 and carries TH_GNU.
+  // only changes deflate_slow, so on levels 1-3 it is the default strategy.  A GNU-family trial (level 1-9,
+  // raw, default strategy: the callers' checks) parses at memLevel 8 and carries TH_GNU.
   // Returns (kind, index in tr[kind]).
-  std::pair<int, uint32_t> add(const Pipe* c, uint32_t s, uint64_t len, int cl, int w, int m, uint32_t strat,
-                               uint8_t mode, uint64_t best_ident) {
-    if (strat == 1 && cl < 4) strat = 0;
-    const int kind = cl == 0 || strat >= 2 ? 0 : cl <= 3 ? 1 : 2;
+  std::pair<int, uint32_t> add(const Pipe* c, uint32_t s, uint64_t len, const DeflSpec& p, uint8_t mode,
+                               uint64_t best_ident) {
+    const uint32_t strat = p.strategy == 1 && p.level < 4 ? 0 : p.strategy;
+    const int kind = p.level == 0 || strat >= 2 ? 0 : p.level <= 3 ? 1 : 2;
     Trial t{};
-    t.stream = s; t.clevel = (uint8_t)cl; t.window = (uint8_t)w; t.memlevel = (uint8_t)(m ? m : 8);
-    t.mode = mode; t.host = strat | (m ? 0u : (uint32_t)TH_GNU) |
-                              ((mode & TM_FLUSH) || (flush_kernels && (mode & TM_RAW) && !strat && m) ? (uint32_t)TH_FLUSH : 0u);
+    t.stream = s; t.clevel = (uint8_t)p.level; t.window = (uint8_t)p.window; t.memlevel = (uint8_t)p.table_memlevel();
+    t.mode = mode | p.mode();
+    t.host = strat | (p.gnu ? (uint32_t)TH_GNU : 0u) |
+             (p.flush || (flush_kernels && p.raw && !strat && !p.gnu) ? (uint32_t)TH_FLUSH : 0u);
     t.best_ident = best_ident;
-    t.out_off = out_tot; t.out_cap = bound(len, w, m) + 64 + ((mode & TM_FLUSH) ? 5 : 0);
+    t.out_off = out_tot; t.out_cap = bound(len, p) + 64 + (p.flush ? 5 : 0);
     out_tot += (t.out_cap + 255) & ~255ull;
-    t.sym_off = sym_tot; sym_tot += sym_words(c, kind, (uint32_t)m, len);
+    t.sym_off = sym_tot; sym_tot += sym_words(c, kind, p, len);
     tr[kind].push_back(t);
     return {kind, (uint32_t)tr[kind].size() - 1};
   }
@@ -3082,18 +3073,17 @@ struct Round : TrialBatch {
         break;
       }
       for (uint32_t j = 0; j < K && st.idx + j < st.list->size(); j++) {
-        const uint32_t p = (*st.list)[st.idx + j];
-        const int cl = (int)(p >> 16), w = (int)((p >> 8) & 0xff), m = (int)(p & 0xff);
+        const DeflSpec p = DeflSpec::from_word((*st.list)[st.idx + j]);
         const uint64_t len = x->recs[s].infl_len;
-        const auto at = add(c, s, len, cl, w, m, 0, 0, st.ident);
+        const auto at = add(c, s, len, p, 0, st.ident);
         const int kind = at.first;
         Trial& t = tr[kind][at.second];
         t.spec_j = j;
-        round_bytes += 8 * (len + 320) + t.out_cap + 4 * sym_words(c, kind, (uint32_t)m, len);
+        round_bytes += 8 * (len + 320) + t.out_cap + 4 * sym_words(c, kind, p, len);
         if (kind) {
           r_bound += ((len + 63) & ~63ull) + 256;
-          need.push_back({s, m});
-          need_b.push_back((uint32_t)(c_cfg_host((uint32_t)cl) >> (kind == 1 ? 0 : 2)));
+          need.push_back({s, p.memlevel});
+          need_b.push_back((uint32_t)(c_cfg_host((uint32_t)p.level) >> (kind == 1 ? 0 : 2)));
         }
         mine.push_back(at);
       }
@@ -3812,37 +3802,11 @@ struct SweepGuard {
 };
 
 // ---------------------------------------------------------------------------------------------
-// Opt-in strategy trials (atz_set_strategies).  The reference never sweeps zlib's
-// strategy, so a Z_FILTERED (libpng's default), Z_RLE or Z_HUFFMAN_ONLY stream ends its walk unrecorded.
-// After the reference walk, unchanged, the streams it left with recomp == 0 get a second walk under the
-// same rule (testDeflateParams and the stop rule, main.cpp:616-700, restarted with identBytes = 0) over
-// the candidates their header's FLEVEL allows -- zlib writes FLEVEL from level and strategy
-// (Z/deflate.c:738-750): 0 for strategy >= Z_HUFFMAN_ONLY, else by level -- at the header's window,
-// memLevels 8, 9, 7..1, levels descending within a memLevel.  Entries: (strategy<<24)|(c<<16)|(w<<8)|m.
-static void strategy_list(std::vector<uint32_t>& l, int type, uint32_t mask) {
-  if (type >= 24) return;   // raw records take no strategy trials
-  const int w = 10 + type / 4;
-  static const int mo[9] = {8, 9, 7, 6, 5, 4, 3, 2, 1};
-  auto add = [&](uint32_t strat, int chi, int clo) {
-    if (!((mask >> strat) & 1u)) return;
-    for (int m : mo)
-      for (int cl = chi; cl >= clo; cl--) l.push_back((strat << 24) | pk(cl, w, m));
-  };
-  switch (type % 4) {
-    case 0: add(3, 6, 6); add(2, 6, 6); break;   // the parse ignores the level: recorded as 6
-    case 1: add(1, 5, 4); break;                 // (levels 1-3 ignore Z_FILTERED: the default list's)
-    case 2: add(1, 6, 6); break;
-    default: add(1, 9, 7); break;
-  }
-}
-
+// Opt-in strategy trials (atz_set_strategies): strategy_list (atz_params.h) and its pass.
 // One round per list position on pipe 0, the streams of a round in batches within the scratch budget (each
 // batch builds the bucket tables its filtered trials read, as deflate_dev does).  A stream the pass
 // records gets clevel = strategy << 4 | level; the others keep what the reference walk left.
 // raw: the same pass over the container extension's records (raw_list; TM_RAW trials), see raw_pass.
-static void raw_list(std::vector<uint32_t>& l, int type, uint32_t defl_mask, bool flush);
-// the memLevel whose bucket and match tables a list entry's trial reads (memLevel 0, a GNU candidate: 8)
-static int tab_memlevel(uint32_t q) { return (q & 0xff) ? (int)(q & 0xff) : 8; }
 static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss, bool raw) {
   const auto t0 = std::chrono::steady_clock::now();
   const size_t n = ss.size();
@@ -3886,26 +3850,25 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
       size_t a1 = a0;
       uint64_t bytes = 0;
       while (a1 < act.size() && (a1 == a0 || bytes <= budget)) {
-        const uint32_t s = act[a1], q = ex[s].list[j];
+        const uint32_t s = act[a1];
+        const DeflSpec q = DeflSpec::from_word(ex[s].list[j]);
         const uint64_t len = c->recs[s].infl_len;
-        bytes += 9 * len + 4 * sym_words(p, 2, q & 0xff, len) + bound(len, (int)((q >> 8) & 0xff), (int)(q & 0xff)) + 4096;
+        bytes += 9 * len + 4 * sym_words(p, 2, q, len) + bound(len, q) + 4096;
         a1++;
       }
       std::vector<std::pair<uint32_t, int>> need;
       for (size_t a = a0; a < a1; a++) {
-        const uint32_t q = ex[act[a]].list[j];
-        if (raw ? ((q >> 16) & 0xff) > 0 : (q >> 24) == 1) need.push_back({act[a], tab_memlevel(q)});
+        const DeflSpec q = DeflSpec::from_word(ex[act[a]].list[j]);
+        if (q.needs_tables()) need.push_back({act[a], q.table_memlevel()});
       }
       if (int r = private_chains(c, p, need)) return r;
       TrialBatch B;   // never saves, replays or stands for a duplicate
       B.flush_kernels = raw && c->seg_mask;
       for (size_t a = a0; a < a1; a++) {
-        const uint32_t s = act[a], q = ex[s].list[j];
-        const int m = (int)(q & 0xff);
-        const auto at = B.add(p, s, c->recs[s].infl_len, (int)((q >> 16) & 0xff), (int)((q >> 8) & 0xff), m, (q >> 24) & 3,
-                              raw ? (uint8_t)(TM_RAW | ((q >> 30) & 1u ? TM_FLUSH : 0)) : 0,
-                              std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len)));
-        if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][tab_memlevel(q)];
+        const uint32_t s = act[a];
+        const DeflSpec q = DeflSpec::from_word(ex[s].list[j]);   // (raw_list's entries carry the raw bit themselves)
+        const auto at = B.add(p, s, c->recs[s].infl_len, q, 0, std::max(ex[s].ident, elig_floor(c, c->recs[s].comp_len)));
+        if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][q.table_memlevel()];
       }
       if (int r = B.reserve(p)) return r;
       std::vector<TrialRes> rr[3];
@@ -3947,9 +3910,8 @@ static int ext_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>&
     const uint64_t C = c->recs[s].comp_len;
     if (!(e.ident > 0 && C - e.ident <= c->o.recomp_tresh)) continue;   // main.cpp:454
     StreamState& st = ss[s];
-    st.c = (uint8_t)((((e.best >> 28) & 1u) << 6) | (((e.best >> 24) & 3u) << 4) | ((e.best >> 16) & 0xff));
-    st.w = (uint8_t)(((e.best >> 8) & 0xff) | (((e.best >> 30) & 1u) << 7));   // (bit 7: flush-terminated)
-    st.m = (uint8_t)(e.best & 0xff);
+    const auto cwm = DeflSpec::from_word(e.best).desc();
+    st.c = cwm[0]; st.w = cwm[1]; st.m = cwm[2];
     st.ident = e.ident;
     st.rawdiff.swap(e.rawdiff); st.diffval.swap(e.diffval);
     st.first_diff = st.rawdiff.empty() ? -1 : (int64_t)st.rawdiff[0];
@@ -3974,31 +3936,7 @@ static int strategy_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamSt
   return c->strat_mask ? ext_pass(c, d_file, ss, false) : 0;
 }
 
-// The raw walk (the container extension): a record of type 24 + hint is a raw deflate body
-// of C = comp_len bytes behind a ZIP or gzip header.  Its candidates: window 15 (what ZIP and gzip writers
-// use; --brute-window does not widen it), the default strategy, memLevels 8, 9, 7..1, and inside a
-// memLevel the levels in the order its container's hint suggests -- 90 entries, raw << 28 | c << 16 |
-// 15 << 8 | m.  The rule is strategy_pass's, on the body: a recorded one gets clevel = 1 << 6 | level.
-// defl_mask bit 0 (atz_set_deflaters): GNU gzip's and Info-ZIP's deflater, levels 1-9 in the
-// hint's order, marked with memLevel 0, directly behind the memLevel-8 group (their parse is zlib's at
-// memLevel 8, so they share its tables) -- 99 entries.
-// flush (a record with flags bit 7, the segment extension's): every entry carries bit 30, which
-// makes its trial TM_FLUSH, and no GNU candidate is added (gzip has no full flush) -- 90 entries.
-static void raw_list(std::vector<uint32_t>& l, int type, uint32_t defl_mask, bool flush) {
-  if (type < 24 || type > 26) return;
-  if (flush) defl_mask = 0;
-  const uint32_t fb = flush ? 1u << 30 : 0u;
-  static const int mo[9] = {8, 9, 7, 6, 5, 4, 3, 2, 1};
-  static const int lo[3][10] = {{6, 9, 1, 5, 7, 8, 4, 3, 2, 0},    // no hint
-                                {1, 2, 3, 4, 5, 6, 7, 8, 9, 0},    // fast
-                                {9, 8, 7, 6, 5, 4, 3, 2, 1, 0}};   // max
-  for (int m : mo) {
-    for (int cl : lo[type - 24]) l.push_back(fb | (1u << 28) | pk(cl, 15, m));
-    if (m == 8 && (defl_mask & 1u))
-      for (int cl : lo[type - 24])
-        if (cl) l.push_back((1u << 28) | pk(cl, 15, 0));
-  }
-}
+// The raw walk (the container extension) over raw_list's candidates (atz_params.h).
 static int raw_pass(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState>& ss) {
   return (c->cont_mask || c->probe_mask || c->seg_mask) ? ext_pass(c, d_file, ss, true) : 0;
 }
@@ -4032,7 +3970,7 @@ static void atz_descriptors(atz_ctx* c, const std::vector<StreamState>& ss, std:
     const size_t m0 = meta.size();   // the stream descriptor goes straight into meta
     put8(meta, r.offset); put8(meta, r.comp_len); put8(meta, r.infl_len);
     // (version 4: bit 7 of the clevel byte marks a stitched descriptor, whose piece list follows its payload)
-    meta.push_back((uint8_t)(st.c | (r.stitch != ~0ull ? 0x80 : 0))); meta.push_back(st.w); meta.push_back(st.m);
+    meta.push_back((uint8_t)(st.c | (r.stitch != ~0ull ? DeflSpec::DESC_STITCHED : 0))); meta.push_back(st.w); meta.push_back(st.m);
     uint64_t nd = st.rawdiff.size();
     put8(meta, nd);
     if (nd) {
@@ -4091,10 +4029,7 @@ static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<
   return 0;
 }
 
-// version 2 (the strategy extension): some descriptor's clevel byte is strategy << 4 | level;
-// version 3 (the container extension): some descriptor's is raw << 6 | strategy << 4 | level
-// version 5 (the deflater extension): some raw descriptor's memLevel byte is 0, a GNU-family body
-// version 6 (the segment extension): some raw descriptor's window byte is 0x8F, a flush-terminated body
+// (the versions: atz_params.h)
 static void atz_header(std::vector<uint8_t>& meta, uint64_t F, uint64_t nrec, uint8_t version = 1) {
   const uint8_t h[4] = {'A', 'T', 'Z', version};
   meta.insert(meta.end(), h, h + 4);
@@ -4108,14 +4043,12 @@ static int write_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::
   std::vector<Seg> segs;
   const size_t n = c->recs.size();
   uint64_t nrec = 0;
-  uint8_t version = 1;   // ATZ1 unless a recorded stream carries a strategy (2), is raw (3), is stitched (4) or is GNU's (5)
+  uint8_t version = 1;   // ATZ1 unless a recorded stream needs more (DeflSpec::min_version)
   size_t npieces = 0;
   for (size_t s = 0; s < n; s++) {
     nrec += ss[s].recomp;
-    if (ss[s].recomp && (ss[s].c >> 4)) version = std::max<uint8_t>(version, (ss[s].c & 0x40) ? 3 : 2);
-    if (ss[s].recomp && c->recs[s].stitch != ~0ull) version = std::max<uint8_t>(version, 4);
-    if (ss[s].recomp && (ss[s].c & 0x40) && ss[s].m == 0) version = std::max<uint8_t>(version, 5);   // a GNU-family body (memLevel byte 0)
-    if (ss[s].recomp && (ss[s].w & 0x80)) version = 6;   // a flush-terminated segment (window byte 0x8F)
+    if (ss[s].recomp)
+      version = std::max(version, DeflSpec::from_desc(ss[s].c, ss[s].w, ss[s].m).min_version(c->recs[s].stitch != ~0ull));
     npieces += c->recs[s].stitch != ~0ull ? c->recs[s].pk : 1;
   }
   atz_header(meta, F, nrec, version);
@@ -4162,23 +4095,9 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   if (!c->scan_keep) c->scan_keep = std::make_shared<ScanState>();
   ScanState& S = *c->scan_keep;
   if (int r = scan_plan(c, h, d_file, F, S)) return r;
-  // the container extension's candidates (none without a mask): the sweep's tables have room for them
-  // (and the stitch extension's, likewise)
-  std::vector<RawCand> raw_cands;
-  StitchPlan stitch_plan;
-  c->st_off.clear(); c->st_len.clear();
-  if (ext_anchor_mask(c)) {
-    std::vector<uint64_t> anchors;
-    if (int r = anchors_dev(c, d_file, F, ext_anchor_mask(c), anchors)) return r;
-    raw_candidates(h, F, anchors, raw_cands);
-    stitch_candidates(h, anchors, stitch_plan);
-  }
-  if (c->probe_mask)   // (the probe extension's survivors, likewise: each may become a record)
-    if (int r = probe_dev(c, d_file, F, c->probe)) return r;
-  if (c->seg_mask)     // (the segment extension's markers: each may add a record)
-    if (int r = markers_dev(c, d_file, F, c->marks)) return r;
-  const size_t n_max = S.max_records() + raw_cands.size() + stitch_plan.cands.size() +
-                       (c->probe_mask ? c->probe.pos.size() : 0) + (c->seg_mask ? c->marks.pos.size() : 0);
+  ScanExt E(c);   // (the extensions' candidates, none without a mask: the sweep's tables have room for them)
+  if (int r = ext_prepare(c, h, d_file, F, E)) return r;
+  const size_t n_max = S.max_records() + E.extra_records();
   c->recs.reserve(n_max);
   std::vector<StreamState>& ss = c->ss_keep;
   SweepRun R;
@@ -4206,7 +4125,7 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   double scan_busy = ms_since(t0);
   // (with a container, stitch, probe or segment mask the added records need the reference's final ones: scan,
   // merge, then sweep)
-  const bool spec = P == 1 && spec_cont_on() && !ext_anchor_mask(c) && !c->probe_mask && !c->seg_mask;
+  const bool spec = P == 1 && spec_cont_on() && !ext_on(c);
   if (spec) {
     // The first continuations of pending streams (each a decode of the stream from its header through
     // the chunk boundary) are latency-bound: one small launch, 15-30 ms.  The records do not wait for
@@ -4271,14 +4190,7 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
     const uint32_t ja = (uint32_t)((uint64_t)nch * p / P), jb = (uint32_t)((uint64_t)nch * (p + 1) / P);
     const size_t r0 = c->recs.size();
     if (int r = scan_piece(c, h, d_file, S, ja, jb)) return r;
-    if (int r = raw_merge(c, h, d_file, S.arena_cap, S.fjobs.empty(), raw_cands)) return r;
-    if (int r = stitch_merge(c, d_file, S.arena_cap, S.fjobs.empty() && raw_cands.empty(), stitch_plan)) return r;
-    if (c->probe_mask)
-      if (int r = probe_merge(c, d_file, F, S.arena_cap,
-                              S.fjobs.empty() && raw_cands.empty() && stitch_plan.cands.empty(), c->probe))
-        return r;
-    if (c->seg_mask)
-      if (int r = seg_merge(c, h, d_file, c->marks)) return r;
+    if (int r = ext_merge(c, h, d_file, F, S, E)) return r;
     if (p == 0) {
       t_begin.join();
       if (rc_begin) return rc_begin;
@@ -4310,7 +4222,7 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
 // match tables / symbol buffers / outputs fit the round budget; after each batch on_batch(s0, s1,
 // out_addr, out_len) sees the outputs (device addresses, valid until the next batch).
 static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std::vector<uint64_t>& len,
-                       const std::vector<uint32_t>& adl, const std::vector<uint32_t>& params,
+                       const std::vector<uint32_t>& adl, const std::vector<DeflSpec>& params,
                        const std::function<int(size_t, size_t, const std::vector<uint64_t>&,
                                                const std::vector<uint64_t>&)>& on_batch) {
   c->scan_valid = false; c->shard.stage = 0;   // recs / infl_off / adler / chain_off are replaced below
@@ -4343,27 +4255,19 @@ static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std:
     // a batch: streams until the scratch estimate passes the budget (at least one)
     size_t s1 = s0;
     uint64_t bytes = 0;
-    // (bit 29: the GNU deflater family, memLevel field 0 -- TrialBatch::add's and sym_words' mark; its tables are
-    // memLevel 8's)
-    auto mlev = [&](size_t s) -> int { return (params[s] >> 29) & 1u ? 0 : (int)(params[s] & 0xff); };
     while (s1 < n && (s1 == s0 || bytes <= budget)) {
-      bytes += 9 * len[s1] + 4 * sym_words(p, 1, (uint32_t)mlev(s1), len[s1]) + 4096;
+      bytes += 9 * len[s1] + 4 * sym_words(p, 1, params[s1], len[s1]) + 4096;
       s1++;
     }
     c->chain_off.assign(n, {});
     std::vector<std::pair<uint32_t, int>> need;
-    // (params carry a strategy in bits 24-25: Z_RLE and Z_HUFFMAN_ONLY read no bucket tables; bit 28: raw output;
-    // bit 30: a flush-terminated body, TM_FLUSH)
     for (size_t s = s0; s < s1; s++)
-      if (((params[s] >> 16) & 0xff) > 0 && ((params[s] >> 24) & 3) < 2) need.push_back({(uint32_t)s, mlev(s) ? mlev(s) : 8});
+      if (params[s].needs_tables()) need.push_back({(uint32_t)s, params[s].table_memlevel()});
     if (int r = private_chains(c, p, need)) return r;
     TrialBatch B;
     for (size_t s = s0; s < s1; s++) {
-      const int m = mlev(s);
-      const auto at = B.add(p, (uint32_t)s, len[s], (int)((params[s] >> 16) & 0xff), (int)((params[s] >> 8) & 0xff), m,
-                            (params[s] >> 24) & 3,
-                            (uint8_t)(TM_FULL | ((params[s] >> 28) & 1u ? TM_RAW : 0) | ((params[s] >> 30) & 1u ? TM_FLUSH : 0)), 0);
-      if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][m ? m : 8];
+      const auto at = B.add(p, (uint32_t)s, len[s], params[s], TM_FULL, 0);
+      if (at.first) B.tr[at.first][at.second].chain_off = c->chain_off[s][params[s].table_memlevel()];
     }
     if (int r = B.reserve(p)) return r;
     SweepOpts so{0, 0, 0, 0};
@@ -4385,7 +4289,7 @@ static int deflate_dev(atz_ctx* c, const std::vector<uint64_t>& addr, const std:
 
 // Host inputs (atz_deflate / atz_deflate_batch): uploaded 256-byte aligned, Adler-32 on the host.
 static int deflate_many(atz_ctx* c, const std::vector<std::pair<const uint8_t*, uint64_t>>& ins,
-                        const std::vector<uint32_t>& params, std::vector<std::vector<uint8_t>>& outs) {
+                        const std::vector<DeflSpec>& params, std::vector<std::vector<uint8_t>>& outs) {
   c->scan_valid = false; c->shard.stage = 0;
   const size_t n = ins.size();
   outs.assign(n, {});
@@ -4445,18 +4349,9 @@ static void stitched_ranges(const uint8_t* atz, const AtzDesc& x, uint64_t a, ui
 // ATZ1 parse with the reference's checks (main.cpp:1011-1063); every size field is bounded by the
 // bytes actually left before anything is sized from it (subtraction-only checks: no sum can wrap)
 static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, uint64_t& origlen, uint64_t& residue) {
-  // version 2: the strategy extension's files (same layout; clevel = strategy << 4 | level)
-  // version 3: the container extension's (clevel = raw << 6 | strategy << 4 | level)
-  // version 4: the stitch extension's (clevel = stitched << 7 | raw << 6 | strategy << 4 | level, never both
-  // of bits 6 and 7; a stitched descriptor's piece list follows its payload: u32 k, k x u32 lengths)
-  // version 5: the deflater extension's (version 4's, and a raw descriptor with the default strategy, level 1-9
-  // and memLevel byte 0 is a GNU-family body)
-  // version 6: the segment extension's (version 5's, and a raw descriptor with the default strategy, memLevel
-  // 1-9 and window byte 0x8F is a flush-terminated body of window 15)
+  // (the versions and what their descriptors may carry: atz_params.h)
   if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 6) return ATZ_E_FORMAT;   // main.cpp:1018-1021
-  const bool v6 = atz[3] == 6;
-  const bool v5 = atz[3] == 5 || v6;
-  const bool v2 = atz[3] == 2, v4 = atz[3] == 4 || v5, v3 = atz[3] == 3 || v4;
+  const int version = atz[3];
   if (rd8(atz + 4) != n) return ATZ_E_FORMAT;                              // main.cpp:1022-1025
   origlen = rd8(atz + 12);
   const uint64_t nstrms = rd8(atz + 20);
@@ -4487,34 +4382,22 @@ static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
       x.fd = 0; x.dpos = 0; x.ipos = lastos + 35;
       lastos = x.ipos + x.il;
     }
-    if (v3) {
-      const uint32_t sg = (x.c >> 4) & 3u;
-      const bool stitched = v4 && (x.c & 0x80);
-      if (((x.c & 0x80) && !v4) || (stitched && (x.c & 0x40)) || (x.c & 15) > 9 || sg > 3 || (sg >= 2 && (x.c & 15) < 1))
-        return ATZ_E_REF_ABORT;
-      if (stitched) {   // k >= 2 pieces, the first and the last not empty, their lengths summing to comp_len
-        if (n - lastos < 4) return ATZ_E_FORMAT;
-        x.k = rd4le(atz + lastos);
-        if (x.k < 2 || x.k > (n - lastos - 4) / 4) return ATZ_E_FORMAT;
-        x.ppos = lastos + 4;
-        lastos = x.ppos + 4 * x.k;
-        uint64_t sum = 0;
-        for (uint64_t i = 0; i < x.k; i++) sum += rd4le(atz + x.ppos + 4 * i);
-        if (sum != x.cl || rd4le(atz + x.ppos) < 1 || rd4le(atz + x.ppos + 4 * (x.k - 1)) < 1) return ATZ_E_FORMAT;
-        x.c &= 0x7f;
-      }
-    } else if (v2) {   // Z_HUFFMAN_ONLY and Z_RLE have no level 0
-      if ((x.c & 15) > 9 || (x.c >> 4) > 3 || ((x.c >> 4) >= 2 && (x.c & 15) < 1)) return ATZ_E_REF_ABORT;
-    } else if (x.c > 9) return ATZ_E_REF_ABORT;
-    if (v5 && x.m == 0) {   // GNU's: raw, not stitched (bit 7 was read above), default strategy, level 1-9, window 15
-      if ((x.c & 0xf0) != 0x40 || (x.c & 15) < 1 || x.w != 15 || x.k) return ATZ_E_REF_ABORT;
-      continue;
+    // a refusal of the parameters: the clevel byte's before the piece list is read, the other bytes' after it
+    const bool ok = valid_desc(version, x.c, x.w, x.m);
+    if (!ok && !valid_desc(version, x.c, 15, 8)) return ATZ_E_REF_ABORT;
+    bool stitched = false;
+    DeflSpec::from_desc(x.c, x.w, x.m, &stitched);
+    if (stitched) {   // k >= 2 pieces, the first and the last not empty, their lengths summing to comp_len
+      if (n - lastos < 4) return ATZ_E_FORMAT;
+      x.k = rd4le(atz + lastos);
+      if (x.k < 2 || x.k > (n - lastos - 4) / 4) return ATZ_E_FORMAT;
+      x.ppos = lastos + 4;
+      lastos = x.ppos + 4 * x.k;
+      uint64_t sum = 0;
+      for (uint64_t i = 0; i < x.k; i++) sum += rd4le(atz + x.ppos + 4 * i);
+      if (sum != x.cl || rd4le(atz + x.ppos) < 1 || rd4le(atz + x.ppos + 4 * (x.k - 1)) < 1) return ATZ_E_FORMAT;
     }
-    if (v6 && (x.w & 0x80)) {   // flush-terminated: window 15, raw, not stitched, default strategy, memLevel 1-9
-      if (x.w != 0x8f || (x.c & 0xf0) != 0x40 || x.k || x.m < 1 || x.m > 9) return ATZ_E_REF_ABORT;
-      continue;
-    }
-    if (x.w < 8 || x.w > 15 || x.m < 1 || x.m > 9) return ATZ_E_REF_ABORT;
+    if (!ok) return ATZ_E_REF_ABORT;
   }
   // streams in file order, inside the original (the writer emits them so; a crafted file with
   // overlapping or out-of-range streams is rejected before any buffer is sized)
@@ -4571,7 +4454,7 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
   if (ns) {
     // payloads into an aligned slab (the trial kernels read 256-byte aligned streams)
     std::vector<uint64_t> loc(ns), addr(ns), len(ns);
-    std::vector<uint32_t> params(ns);
+    std::vector<DeflSpec> params(ns);
     uint64_t tot = 0;
     for (size_t j = 0; j < ns; j++) { loc[j] = tot; tot += (d[j].il + 255) & ~255ull; }
     if (c->slabs.empty()) c->slabs.emplace_back(new DBuf());
@@ -4582,11 +4465,8 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
       if (d[j].il) segs.push_back({2, 0, d[j].ipos, loc[j], d[j].il});
       addr[j] = (uint64_t)(uintptr_t)slab.p + loc[j];
       len[j] = d[j].il;
-      const int w = d[j].w == 8 ? 9 : d[j].w & 0x7f;
-      params[j] = ((uint32_t)(d[j].w >> 7) << 30) |   // a flush-terminated body (parse_atz: version 6 only)
-                  ((uint32_t)((d[j].c >> 6) & 1) << 28) | ((uint32_t)((d[j].c >> 4) & 3) << 24) |
-                  ((uint32_t)(d[j].c & 15) << 16) | ((uint32_t)w << 8) | d[j].m;
-      if (d[j].m == 0) params[j] |= 1u << 29;   // a GNU-family body (parse_atz: version 5 only)
+      params[j] = DeflSpec::from_desc(d[j].c, d[j].w, d[j].m);
+      if (params[j].window == 8) params[j].window = 9;   // as zlib's deflateInit2 does
     }
     if (!segs.empty())
       if (int r = gather_segments(c, d_atz, meta, segs, slab.as<uint8_t>())) return r;
@@ -5143,10 +5023,10 @@ int atz_deflate(atz_ctx_t* c, const uint8_t* in, uint64_t in_len, int clevel, in
     if (!c || (!in && in_len) || !out_len || clevel < 0 || clevel > 9 || window < 8 || window > 15 ||
         memlevel < 1 || memlevel > 9)
       return ATZ_E_ARG;
-    if (window == 8) window = 9;
+    DeflSpec p;
+    p.level = clevel; p.window = window == 8 ? 9 : window; p.memlevel = memlevel;
     std::vector<std::vector<uint8_t>> outs;
-    if (int r = deflate_many(c, {{in, in_len}}, {((uint32_t)clevel << 16) | ((uint32_t)window << 8) | (uint32_t)memlevel}, outs))
-      return r;
+    if (int r = deflate_many(c, {{in, in_len}}, {p}, outs)) return r;
     *out_len = outs[0].size();
     if (outs[0].size() > out_cap) return ATZ_E_ARG;
     if (out && !outs[0].empty()) std::memcpy(out, outs[0].data(), outs[0].size());
@@ -5154,9 +5034,7 @@ int atz_deflate(atz_ctx_t* c, const uint8_t* in, uint64_t in_len, int clevel, in
   });
 }
 
-// ex: params carry zlib's strategy in bits 24-27, the raw flag in bit 28, the GNU deflater in bit 29 and the flush
-// end in bit 30 (atz_deflate_batch_ex); else
-// bits 16-31 are the level
+// ex: atz_deflate_batch_ex's reading of the params words (valid_api, atz_params.h)
 static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, const uint64_t* offs, const uint64_t* lens,
                              const uint32_t* params, uint64_t n, uint8_t* out, const uint64_t* out_offs,
                              const uint64_t* out_caps, uint64_t* out_lens, bool ex) {
@@ -5164,24 +5042,10 @@ static int deflate_batch_api(atz_ctx_t* c, const uint8_t* buf, uint64_t len, con
     (void)hipGetLastError();
     if (!c || (!buf && len) || !out_lens) return ATZ_E_ARG;
     std::vector<std::pair<const uint8_t*, uint64_t>> ins(n);
-    std::vector<uint32_t> ps(n);
+    std::vector<DeflSpec> ps(n);
     for (uint64_t k = 0; k < n; k++) {
-      if (offs[k] + lens[k] > len) return ATZ_E_ARG;
-      const uint32_t raw = ex ? (params[k] >> 28) & 1u : 0u;   // no zlib header, no Adler-32 trailer
-      const uint32_t gnu = ex ? (params[k] >> 29) & 1u : 0u;   // the GNU deflater family: raw, window 15, level 1-9 only
-      const uint32_t fl = ex ? (params[k] >> 30) & 1u : 0u;    // a flush-terminated body: raw, zlib's, default strategy only
-      const int sg = ex ? (int)((params[k] >> 24) & ~(16u | 32u | 64u)) : 0;
-      int cl = (int)(ex ? (params[k] >> 16) & 0xff : params[k] >> 16), w = (int)((params[k] >> 8) & 0xff), m = (int)(params[k] & 0xff);
-      if (gnu) {   // (the memLevel field is ignored)
-        if (!raw || sg != 0 || w != 15 || cl < 1 || cl > 9) return ATZ_E_ARG;
-        m = 0;
-      } else if (m < 1 || m > 9) return ATZ_E_ARG;
-      if (fl && (!raw || gnu || sg != 0 || w < 9)) return ATZ_E_ARG;
-      if (cl < 0 || cl > 9 || w < 8 || w > 15) return ATZ_E_ARG;
-      if (sg > 3 || (sg >= 2 && cl < 1)) return ATZ_E_ARG;   // Z_FIXED is not supported; Z_RLE / Z_HUFFMAN_ONLY have no level 0
-      if (w == 8) w = 9;
+      if (offs[k] + lens[k] > len || !valid_api(params[k], ex, &ps[k])) return ATZ_E_ARG;
       ins[k] = {buf + offs[k], lens[k]};
-      ps[k] = (fl << 30) | (gnu << 29) | (raw << 28) | ((uint32_t)sg << 24) | ((uint32_t)cl << 16) | ((uint32_t)w << 8) | (uint32_t)m;
     }
     std::vector<std::vector<uint8_t>> outs;
     if (int r = deflate_many(c, ins, ps, outs)) return r;

@@ -339,6 +339,27 @@ static bool write_file(const std::string& n, const uint8_t* p, uint64_t len) {
   f.write(reinterpret_cast<const char*>(p), (std::streamsize)len);
   return (bool)f;
 }
+// The mask an extension's environment variable asks for: its words, split at commas (empty ones skipped), by
+// the table; an unknown word is an error ("<var>: unknown <noun> <word>").  Unset: mask stays 0.
+struct Word { const char* word; uint32_t bit; };
+static bool env_mask(const char* var, std::initializer_list<Word> table, const char* noun, uint32_t& mask) {
+  const char* e = std::getenv(var);
+  if (!e) return true;
+  std::stringstream words(e);
+  std::string w;
+  while (std::getline(words, w, ',')) {
+    if (w.empty()) continue;
+    uint32_t bit = 0;
+    for (const Word& t : table)
+      if (w == t.word) bit = t.bit;
+    if (!bit) {
+      std::cerr << "Error Encountered: " << var << ": unknown " << noun << " " << w << std::endl;
+      return false;
+    }
+    mask |= bit;
+  }
+  return true;
+}
 
 int main(int argc, char* argv[]) {
   std::cout << "AntiZ " << ANTIZ_VER << std::endl;
@@ -436,99 +457,22 @@ int main(int argc, char* argv[]) {
     std::cerr << "Error Encountered: " << "failed to open File " << in << std::endl;
     return done(1);
   }
-  // ATZ_STRATEGIES=filtered,rle,huffman (any subset; not a reference flag): zlib strategies to try on the
-  // streams the reference's walk leaves unrecorded (atz_set_strategies)
-  uint32_t strategies = 0;
-  if (const char* e = std::getenv("ATZ_STRATEGIES")) {
-    std::stringstream words(e);
-    std::string w;
-    while (std::getline(words, w, ',')) {
-      if (w.empty()) continue;
-      if (w == "filtered") strategies |= 1u << 1;
-      else if (w == "huffman") strategies |= 1u << 2;
-      else if (w == "rle") strategies |= 1u << 3;
-      else {
-        std::cerr << "Error Encountered: " << "ATZ_STRATEGIES: unknown strategy " << w << std::endl;
-        return done(1);
-      }
-    }
-  }
-  // ATZ_CONTAINERS=zip,gzip (any subset; not a reference flag): also recompress the raw deflate bodies of
-  // ZIP entries and gzip members (atz_set_containers)
-  uint32_t containers = 0;
-  if (const char* e = std::getenv("ATZ_CONTAINERS")) {
-    std::stringstream words(e);
-    std::string w;
-    while (std::getline(words, w, ',')) {
-      if (w.empty()) continue;
-      if (w == "zip") containers |= 1u << 0;
-      else if (w == "gzip") containers |= 1u << 1;
-      else {
-        std::cerr << "Error Encountered: " << "ATZ_CONTAINERS: unknown container " << w << std::endl;
-        return done(1);
-      }
-    }
-  }
-  // ATZ_STITCH=png (not a reference flag): also recompress zlib streams split over the IDAT chunks of a PNG
-  // (atz_set_stitch)
-  uint32_t stitch = 0;
-  if (const char* e = std::getenv("ATZ_STITCH")) {
-    std::stringstream words(e);
-    std::string w;
-    while (std::getline(words, w, ',')) {
-      if (w.empty()) continue;
-      if (w == "png") stitch |= 1u << 0;
-      else {
-        std::cerr << "Error Encountered: " << "ATZ_STITCH: unknown stitcher " << w << std::endl;
-        return done(1);
-      }
-    }
-  }
-  // ATZ_PROBE=deflate (not a reference flag): also test every byte position for the start of a raw deflate
-  // stream that no header or container announces (atz_set_probe)
-  uint32_t probe = 0;
-  if (const char* e = std::getenv("ATZ_PROBE")) {
-    std::stringstream words(e);
-    std::string w;
-    while (std::getline(words, w, ',')) {
-      if (w.empty()) continue;
-      if (w == "deflate") probe |= 1u << 0;
-      else {
-        std::cerr << "Error Encountered: " << "ATZ_PROBE: unknown probe " << w << std::endl;
-        return done(1);
-      }
-    }
-  }
-  // ATZ_DEFLATERS=gnu (not a reference flag): the raw records' walk also tries the deflater of GNU gzip and
-  // Info-ZIP's zip (atz_set_deflaters)
-  uint32_t deflaters = 0;
-  if (const char* e = std::getenv("ATZ_DEFLATERS")) {
-    std::stringstream words(e);
-    std::string w;
-    while (std::getline(words, w, ',')) {
-      if (w.empty()) continue;
-      if (w == "gnu") deflaters |= 1u << 0;
-      else {
-        std::cerr << "Error Encountered: " << "ATZ_DEFLATERS: unknown deflater " << w << std::endl;
-        return done(1);
-      }
-    }
-  }
-  // ATZ_SEGMENTS=flush (not a reference flag): streams cut by full-flush points are recorded segment by segment
-  // (atz_set_segments)
-  uint32_t segments = 0;
-  if (const char* e = std::getenv("ATZ_SEGMENTS")) {
-    std::stringstream words(e);
-    std::string w;
-    while (std::getline(words, w, ',')) {
-      if (w.empty()) continue;
-      if (w == "flush") segments |= 1u << 0;
-      else {
-        std::cerr << "Error Encountered: " << "ATZ_SEGMENTS: unknown segment kind " << w << std::endl;
-        return done(1);
-      }
-    }
-  }
+  // The opt-in extensions (not reference flags), each a comma-separated subset of its words:
+  // ATZ_STRATEGIES: zlib strategies to try on the streams the reference's walk leaves unrecorded (atz_set_strategies)
+  // ATZ_CONTAINERS: also recompress the raw deflate bodies of ZIP entries and gzip members (atz_set_containers)
+  // ATZ_STITCH: also recompress zlib streams split over the IDAT chunks of a PNG (atz_set_stitch)
+  // ATZ_PROBE: also test every byte position for the start of a raw deflate stream that no header or container
+  // announces (atz_set_probe)
+  // ATZ_DEFLATERS: the raw records' walk also tries the deflater of GNU gzip and Info-ZIP's zip (atz_set_deflaters)
+  // ATZ_SEGMENTS: streams cut by full-flush points are recorded segment by segment (atz_set_segments)
+  uint32_t strategies = 0, containers = 0, stitch = 0, probe = 0, deflaters = 0, segments = 0;
+  if (!env_mask("ATZ_STRATEGIES", {{"filtered", 1u << 1}, {"huffman", 1u << 2}, {"rle", 1u << 3}}, "strategy", strategies) ||
+      !env_mask("ATZ_CONTAINERS", {{"zip", 1u << 0}, {"gzip", 1u << 1}}, "container", containers) ||
+      !env_mask("ATZ_STITCH", {{"png", 1u << 0}}, "stitcher", stitch) ||
+      !env_mask("ATZ_PROBE", {{"deflate", 1u << 0}}, "probe", probe) ||
+      !env_mask("ATZ_DEFLATERS", {{"gnu", 1u << 0}}, "deflater", deflaters) ||
+      !env_mask("ATZ_SEGMENTS", {{"flush", 1u << 0}}, "segment kind", segments))
+    return done(1);
   if (open_ctx()) return done(255);
   if (segments && atz_set_segments(ctx, segments) != 0) return done(255);
   if (deflaters && atz_set_deflaters(ctx, deflaters) != 0) return done(255);
