@@ -43,17 +43,13 @@
 
 #include "../../include/atz_accel.h"
 #include "atz_params.h"
+#include "atz_format.h"
 
 using namespace atz;
 
 namespace {
 
-struct Seg {           // k_gather segment
-  uint32_t src;        // 0 meta, 1 inflated (absolute address), 2 file, 3 zeros
-  uint32_t pad;
-  uint64_t src_off, dst_off, len;
-};
-
+// (Seg, the k_gather segment: atz_format.h)
 __global__ __launch_bounds__(256) void k_gather(const uint8_t* __restrict__ meta, const uint8_t* __restrict__ infl,
                                                const uint8_t* __restrict__ file, uint8_t* __restrict__ dst,
                                                const Seg* __restrict__ segs, uint32_t nseg) {
@@ -61,11 +57,11 @@ __global__ __launch_bounds__(256) void k_gather(const uint8_t* __restrict__ meta
   for (uint32_t s = blockIdx.x * 4 + wave; s < nseg; s += gridDim.x * 4) {
     const Seg g = segs[s];
     uint8_t* d = dst + g.dst_off;
-    if (g.src == 3) {
+    if (g.src == SEG_ZERO) {
       for (uint64_t k = lane; k < g.len; k += 64) d[k] = 0;
       continue;
     }
-    const uint8_t* src = (g.src == 0 ? meta : g.src == 1 ? infl : file) + g.src_off;
+    const uint8_t* src = (g.src == SEG_META ? meta : g.src == SEG_ADDR ? infl : file) + g.src_off;
     // head bytes up to a 4-byte aligned destination, then aligned dword stores whose 4 source bytes
     // come from two aligned dword loads joined with v_alignbyte (any source alignment), 4 per lane in
     // flight, then the tail bytes.  Reads stay inside the source's 4-byte words that hold segment bytes.
@@ -945,8 +941,6 @@ static void chunk_bytes(const uint8_t* f, const Chunk& ch, std::vector<uint8_t>&
   v.insert(v.end(), f + ch.co + 1, f + ch.co + ch.len);
 }
 
-static uint64_t rd8(const uint8_t* p) { uint64_t v; std::memcpy(&v, p, 8); return v; }
-
 // ATZ_TIMING=1: host phase timings on stderr
 #define TMARK(name)                                                                        \
   do {                                                                                     \
@@ -1194,8 +1188,8 @@ static int scan_continuations(atz_ctx* c, const uint8_t* h, const uint8_t* d_fil
       std::vector<Seg> segs;
       std::vector<uint8_t> meta;
       uint64_t out = 0;
-      auto add_file = [&](uint64_t off, uint64_t len) { if (len) segs.push_back({2, 0, off, out, len}); out += len; };
-      auto add_byte = [&](uint8_t b) { segs.push_back({0, 0, meta.size(), out, 1}); meta.push_back(b); out += 1; };
+      auto add_file = [&](uint64_t off, uint64_t len) { if (len) segs.push_back({SEG_FILE, 0, off, out, len}); out += len; };
+      auto add_byte = [&](uint8_t b) { segs.push_back({SEG_META, 0, meta.size(), out, 1}); meta.push_back(b); out += 1; };
       std::vector<InfJob> cj;
       std::vector<bool> cut;
       for (uint32_t j : todo) {
@@ -1601,8 +1595,22 @@ static void stitch_candidates(const uint8_t* h, const std::vector<uint64_t>& anc
   }
 }
 
+// k_gather of the segments into dst (device): metadata, resident payloads, file ranges
 static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<uint8_t>& meta,
-                           const std::vector<Seg>& segs, uint8_t* dst);
+                           const std::vector<Seg>& segs, uint8_t* dst) {
+  if (int r = upload(c, c->d_meta, meta.data(), meta.size())) return r;
+  if (int r = upload(c, c->d_segs, segs.data(), segs.size() * sizeof(Seg))) return r;
+  const uint32_t nseg = (uint32_t)segs.size();
+  const uint32_t blocks = std::min<uint32_t>((nseg + 3) / 4, 65535u);
+  kbeg(c, 3);
+  hipLaunchKernelGGL(k_gather, dim3(blocks ? blocks : 1), dim3(256), 0, c->st, c->d_meta.as<uint8_t>(),
+                     INFL_BASE, d_file, dst, c->d_segs.as<Seg>(), nseg);
+  kend(c);
+  KCHECK("k_gather");
+  HIPCHK(hipStreamSynchronize(c->st));
+  kcollect(c);
+  return 0;
+}
 
 // The stitched records of the file merged into c->recs (the reference's and the raw ones, complete, in file
 // order).  The stitch buffer holds every candidate's run; the chains are disjoint, so the payload bytes
@@ -1620,7 +1628,7 @@ static int stitch_merge(atz_ctx* c, const uint8_t* d_file, uint64_t arena_cap, b
     const StitchCand& a = P.cands[k];
     uint64_t at = a.at;
     for (uint32_t q = a.p0; q < a.p0 + a.pk; q++) {
-      if (P.len[q]) segs.push_back({2, 0, P.off[q], at, P.len[q]});
+      if (P.len[q]) segs.push_back({SEG_FILE, 0, P.off[q], at, P.len[q]});
       at += P.len[q];
     }
     jobs[k] = {a.at, a.total, ARENA_OUT, ARENA_SLOT};
@@ -1919,7 +1927,7 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
     const Rec& r = c->recs[s];
     c->infl_off[s] = base + loc[s - r0];
     if (r.arena_off != ~0ull) {
-      segs.push_back({0, 0, r.arena_off, loc[s - r0], r.infl_len});
+      segs.push_back({SEG_META, 0, r.arena_off, loc[s - r0], r.infl_len});
     } else {
       InfJob jb;
       jb.in_off = r.offset; jb.in_len = r.comp_len; jb.out_off = loc[s - r0]; jb.out_cap = r.infl_len;
@@ -3955,85 +3963,19 @@ static int sweep_impl(atz_ctx* c, const uint8_t* d_file, std::vector<StreamState
 
 // ---------------------------------------------------------------------------------------------
 // Phase 4: ATZ1 assembled in HBM
-static void put8(std::vector<uint8_t>& m, uint64_t v) { uint8_t b[8]; std::memcpy(b, &v, 8); m.insert(m.end(), b, b + 8); }
-
-// Stream descriptors + inflated payloads of the recompressed streams, in record order
-// (writeStreamdesc, main.cpp:805-831): metadata bytes into `meta`, copy segments into `segs`.
-static void atz_descriptors(atz_ctx* c, const std::vector<StreamState>& ss, std::vector<uint8_t>& meta,
-                            std::vector<Seg>& segs, uint64_t& out) {
-  const size_t n = ss.size();
-  segs.reserve(segs.size() + 2 * n + 8);
-  for (size_t s = 0; s < n; s++) {
-    const StreamState& st = ss[s];
-    if (!st.recomp) continue;
+// The context's records as the writer takes them (atz_format.h); the pointers are into ss, infl_off, st_off / st_len.
+static auto write_recs(const atz_ctx* c, const std::vector<StreamState>& ss) {
+  return [c, &ss](size_t s) {
     const Rec& r = c->recs[s];
-    const size_t m0 = meta.size();   // the stream descriptor goes straight into meta
-    put8(meta, r.offset); put8(meta, r.comp_len); put8(meta, r.infl_len);
-    // (version 4: bit 7 of the clevel byte marks a stitched descriptor, whose piece list follows its payload)
-    meta.push_back((uint8_t)(st.c | (r.stitch != ~0ull ? DeflSpec::DESC_STITCHED : 0))); meta.push_back(st.w); meta.push_back(st.m);
-    uint64_t nd = st.rawdiff.size();
-    put8(meta, nd);
-    if (nd) {
-      put8(meta, (uint64_t)st.first_diff);
-      for (uint64_t k = 0; k < nd; k++) put8(meta, k == 0 ? 0 : (uint64_t)st.rawdiff[k] - st.rawdiff[k - 1]);
-      meta.insert(meta.end(), st.diffval.begin(), st.diffval.end());
-    }
-    segs.push_back({0, 0, m0, out, meta.size() - m0});
-    out += meta.size() - m0;
-    segs.push_back({1, 0, c->infl_off[s], out, r.infl_len});   // absolute address (INFL_BASE)
-    out += r.infl_len;
-    if (r.stitch != ~0ull) {   // u32 k, k x u32 piece lengths (piece i starts at offset + sum_{j<i} (len_j + 12))
-      const size_t m1 = meta.size();
-      auto put4 = [&](uint32_t v) { uint8_t b[4]; std::memcpy(b, &v, 4); meta.insert(meta.end(), b, b + 4); };
-      put4(r.pk);
-      for (uint32_t q = r.p0; q < r.p0 + r.pk; q++) put4((uint32_t)c->st_len[q]);
-      segs.push_back({0, 0, m1, out, meta.size() - m1});
-      out += meta.size() - m1;
-    }
-  }
-}
-
-// The residue (main.cpp:784-796): every file byte outside the recompressed streams, in order.
-// rec[k] = (offset, comp_len) of every record of the file, recomp[k] its decision.
-static int atz_residue(const std::vector<std::pair<uint64_t, uint64_t>>& rec, const uint8_t* recomp, uint64_t F,
-                       std::vector<Seg>& segs, uint64_t& out) {
-  uint64_t lastos = 0, lastlen = 0;
-  for (size_t s = 0; s < rec.size(); s++) {
-    const uint64_t off = rec[s].first, len = rec[s].second;
-    if (lastos + lastlen != off) {
-      if (off < lastos + lastlen) return ATZ_E_REF_UB;   // copyto() with a wrapped length
-      segs.push_back({2, 0, lastos + lastlen, out, off - (lastos + lastlen)});
-      out += off - (lastos + lastlen);
-    }
-    if (!recomp[s]) { segs.push_back({2, 0, off, out, len}); out += len; }
-    lastos = off; lastlen = len;
-  }
-  if (lastos + lastlen < F) { segs.push_back({2, 0, lastos + lastlen, out, F - (lastos + lastlen)}); out += F - (lastos + lastlen); }
-  return 0;
-}
-
-// k_gather of the segments into dst (device): metadata, resident payloads, file ranges
-static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<uint8_t>& meta,
-                           const std::vector<Seg>& segs, uint8_t* dst) {
-  if (int r = upload(c, c->d_meta, meta.data(), meta.size())) return r;
-  if (int r = upload(c, c->d_segs, segs.data(), segs.size() * sizeof(Seg))) return r;
-  const uint32_t nseg = (uint32_t)segs.size();
-  const uint32_t blocks = std::min<uint32_t>((nseg + 3) / 4, 65535u);
-  kbeg(c, 3);
-  hipLaunchKernelGGL(k_gather, dim3(blocks ? blocks : 1), dim3(256), 0, c->st, c->d_meta.as<uint8_t>(),
-                     INFL_BASE, d_file, dst, c->d_segs.as<Seg>(), nseg);
-  kend(c);
-  KCHECK("k_gather");
-  HIPCHK(hipStreamSynchronize(c->st));
-  kcollect(c);
-  return 0;
-}
-
-// (the versions: atz_params.h)
-static void atz_header(std::vector<uint8_t>& meta, uint64_t F, uint64_t nrec, uint8_t version = 1) {
-  const uint8_t h[4] = {'A', 'T', 'Z', version};
-  meta.insert(meta.end(), h, h + 4);
-  put8(meta, 0); put8(meta, F); put8(meta, nrec);   // length back-patched (main.cpp:776, 797-800)
+    const StreamState& st = ss[s];
+    WriteRec x;
+    x.off = r.offset; x.comp_len = r.comp_len; x.infl_len = r.infl_len;
+    x.recomp = st.recomp; x.c = st.c; x.w = st.w; x.m = st.m;
+    x.first_diff = st.first_diff; x.nd = st.rawdiff.size(); x.pos = st.rawdiff.data(); x.val = st.diffval.data();
+    x.payload = c->infl_off[s];   // absolute address (INFL_BASE)
+    if (r.stitch != ~0ull) { x.k = r.pk; x.piece_off = c->st_off.data() + r.p0; x.piece_len = c->st_len.data() + r.p0; }
+    return x;
+  };
 }
 
 static int write_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::vector<StreamState>& ss,
@@ -4041,32 +3983,8 @@ static int write_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::
   auto t0 = std::chrono::steady_clock::now();
   std::vector<uint8_t> meta;
   std::vector<Seg> segs;
-  const size_t n = c->recs.size();
-  uint64_t nrec = 0;
-  uint8_t version = 1;   // ATZ1 unless a recorded stream needs more (DeflSpec::min_version)
-  size_t npieces = 0;
-  for (size_t s = 0; s < n; s++) {
-    nrec += ss[s].recomp;
-    if (ss[s].recomp)
-      version = std::max(version, DeflSpec::from_desc(ss[s].c, ss[s].w, ss[s].m).min_version(c->recs[s].stitch != ~0ull));
-    npieces += c->recs[s].stitch != ~0ull ? c->recs[s].pk : 1;
-  }
-  atz_header(meta, F, nrec, version);
-  segs.push_back({0, 0, 0, 0, meta.size()});
-  uint64_t out = meta.size();
-  meta.reserve(meta.size() + nrec * 43 + 64);
-  atz_descriptors(c, ss, meta, segs, out);
-  // (a stitched record occupies one range per piece: the framing between them is residue)
-  std::vector<std::pair<uint64_t, uint64_t>> rec;
-  std::vector<uint8_t> rc;
-  rec.reserve(npieces); rc.reserve(npieces);
-  for (size_t s = 0; s < n; s++) {
-    const Rec& r = c->recs[s];
-    if (r.stitch == ~0ull) { rec.push_back({r.offset, r.comp_len}); rc.push_back(ss[s].recomp); continue; }
-    for (uint32_t q = r.p0; q < r.p0 + r.pk; q++) { rec.push_back({c->st_off[q], c->st_len[q]}); rc.push_back(ss[s].recomp); }
-  }
-  if (int r = atz_residue(rec, rc.data(), F, segs, out)) return r;
-  std::memcpy(meta.data() + 4, &out, 8);   // back-patched length (main.cpp:797-800)
+  uint64_t out = 0;
+  if (int r = write_file(c->recs.size(), write_recs(c, ss), F, meta, segs, out)) return r;
   if (int r = c->d_atz.reserve(out + 4096)) return r;
   if (int r = gather_segments(c, d_file, meta, segs, c->d_atz.as<uint8_t>())) return r;
   *atz_len = out;
@@ -4323,98 +4241,11 @@ static int deflate_many(atz_ctx* c, const std::vector<std::pair<const uint8_t*, 
 
 // ---------------------------------------------------------------------------------------------
 // Reconstruct (-r; ATZreconstructor::reconstructATZ, main.cpp:869-950) with the ATZ1 bytes resident
-// in HBM: descriptors parsed on the host (h: host copy), payloads gathered into an aligned slab,
-// Adler-32 on the device, one deflate per stream (doDeflate, main.cpp:976-1003), diff bytes patched
-// (main.cpp:916-926) and the original assembled in c->d_rec by k_gather: residue gaps, the first
-// comp_len bytes of each deflate output (zero-extended, as the reference's buffer is), the tail.
-// (k, ppos: a stitched descriptor's piece count and the position of its k u32 piece lengths; k = 0: not stitched)
-struct AtzDesc {
-  uint64_t off, cl, il, nd, fd, dpos, ipos; uint8_t c, w, m;
-  uint64_t k = 0, ppos = 0;
-  uint64_t hull() const { return cl + (k ? 12 * (k - 1) : 0); }
-};
-static uint32_t rd4le(const uint8_t* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
-// stream range [a, b) of a stitched descriptor, cut at its pieces: fn(stream position, file position, length)
-template <class F>
-static void stitched_ranges(const uint8_t* atz, const AtzDesc& x, uint64_t a, uint64_t b, F fn) {
-  uint64_t sp = 0, fp = x.off;   // the piece's first byte in the stream and in the file
-  for (uint64_t i = 0; i < x.k && sp < b; i++) {
-    const uint64_t len = rd4le(atz + x.ppos + 4 * i);
-    const uint64_t lo = std::max(a, sp), hi = std::min(b, sp + len);
-    if (lo < hi) fn(lo, fp + (lo - sp), hi - lo);
-    sp += len; fp += len + 12;
-  }
-}
-
-// ATZ1 parse with the reference's checks (main.cpp:1011-1063); every size field is bounded by the
-// bytes actually left before anything is sized from it (subtraction-only checks: no sum can wrap)
-static int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, uint64_t& origlen, uint64_t& residue) {
-  // (the versions and what their descriptors may carry: atz_params.h)
-  if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > 6) return ATZ_E_FORMAT;   // main.cpp:1018-1021
-  const int version = atz[3];
-  if (rd8(atz + 4) != n) return ATZ_E_FORMAT;                              // main.cpp:1022-1025
-  origlen = rd8(atz + 12);
-  const uint64_t nstrms = rd8(atz + 20);
-  d.clear();
-  if (nstrms == 0) {
-    if (origlen > n - 28) return ATZ_E_FORMAT;
-    residue = 28;
-    return 0;
-  }
-  if (nstrms > (n - 28) / 35) return ATZ_E_FORMAT;                       // each descriptor is >= 35 bytes
-  d.resize(nstrms);
-  uint64_t lastos = 28;                                                    // main.cpp:1031-1063
-  for (uint64_t j = 0; j < nstrms; j++) {
-    if (n - lastos < 35) return ATZ_E_FORMAT;
-    AtzDesc& x = d[j];
-    x.off = rd8(atz + lastos); x.cl = rd8(atz + lastos + 8); x.il = rd8(atz + lastos + 16);
-    x.c = atz[lastos + 24]; x.w = atz[lastos + 25]; x.m = atz[lastos + 26];
-    x.nd = rd8(atz + lastos + 27);
-    if (x.nd) {
-      if (n - lastos < 43) return ATZ_E_FORMAT;
-      const uint64_t room = n - lastos - 43;
-      if (x.nd > room / 9) return ATZ_E_FORMAT;
-      if (x.il > room - x.nd * 9) return ATZ_E_FORMAT;
-      x.fd = rd8(atz + lastos + 35); x.dpos = lastos + 43; x.ipos = lastos + 43 + x.nd * 9;
-      lastos = x.ipos + x.il;
-    } else {
-      if (x.il > n - lastos - 35) return ATZ_E_FORMAT;
-      x.fd = 0; x.dpos = 0; x.ipos = lastos + 35;
-      lastos = x.ipos + x.il;
-    }
-    // a refusal of the parameters: the clevel byte's before the piece list is read, the other bytes' after it
-    const bool ok = valid_desc(version, x.c, x.w, x.m);
-    if (!ok && !valid_desc(version, x.c, 15, 8)) return ATZ_E_REF_ABORT;
-    bool stitched = false;
-    DeflSpec::from_desc(x.c, x.w, x.m, &stitched);
-    if (stitched) {   // k >= 2 pieces, the first and the last not empty, their lengths summing to comp_len
-      if (n - lastos < 4) return ATZ_E_FORMAT;
-      x.k = rd4le(atz + lastos);
-      if (x.k < 2 || x.k > (n - lastos - 4) / 4) return ATZ_E_FORMAT;
-      x.ppos = lastos + 4;
-      lastos = x.ppos + 4 * x.k;
-      uint64_t sum = 0;
-      for (uint64_t i = 0; i < x.k; i++) sum += rd4le(atz + x.ppos + 4 * i);
-      if (sum != x.cl || rd4le(atz + x.ppos) < 1 || rd4le(atz + x.ppos + 4 * (x.k - 1)) < 1) return ATZ_E_FORMAT;
-    }
-    if (!ok) return ATZ_E_REF_ABORT;
-  }
-  // streams in file order, inside the original (the writer emits them so; a crafted file with
-  // overlapping or out-of-range streams is rejected before any buffer is sized)
-  uint64_t end = 0;
-  for (uint64_t j = 0; j < nstrms; j++) {
-    if (d[j].off < end || d[j].off > origlen || d[j].cl > origlen - d[j].off) return ATZ_E_FORMAT;
-    if (d[j].k && (d[j].k - 1 > (origlen - d[j].off - d[j].cl) / 12)) return ATZ_E_FORMAT;   // the hull inside the original
-    end = d[j].off + d[j].hull();
-  }
-  residue = lastos;
-  // the residue must hold every gap and the tail
-  uint64_t gaps = origlen;
-  for (const AtzDesc& x : d) gaps -= x.cl;
-  if (gaps > n - residue) return ATZ_E_FORMAT;
-  return 0;
-}
-
+// in HBM: descriptors parsed on the host (h: host copy) and the plan made there (atz_format.h: parse_atz,
+// plan_layout, plan_batch), payloads gathered into an aligned slab, Adler-32 on the device, one deflate
+// per stream (doDeflate, main.cpp:976-1003), diff bytes patched (main.cpp:916-926) and the original
+// assembled in c->d_rec by k_gather: residue gaps, the first comp_len bytes of each deflate output
+// (zero-extended, as the reference's buffer is), the tail.
 static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, uint64_t n, uint64_t* out_len) {
   auto t0 = std::chrono::steady_clock::now();
   std::vector<AtzDesc> d;
@@ -4422,54 +4253,21 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
   if (int r = parse_atz(h, n, d, origlen, residue)) return r;
   if (int r = c->d_rec.reserve(origlen + 4096)) return r;
   const size_t ns = d.size();
-  std::vector<Seg> segs;
-  std::vector<uint8_t> meta(8, 0);
-  uint64_t gapsum = 0, lo = 0, ll = 0, out = 0;
+  RecLayout L;
+  if (int r = plan_layout(h, n, d, origlen, residue, L)) return r;
+  const std::vector<uint8_t> meta(8, 0);
   // residue gaps and the tail are plain copies; the streams' segments come from their batches
-  // (a stitched stream's pieces each take their place: the 12 framing bytes between two are a gap)
-  std::vector<uint64_t> rec_off(ns);
-  auto place = [&](uint64_t off, uint64_t len) {
-    if (lo + ll != off) {
-      const uint64_t g = off - (lo + ll);   // > 0: offsets checked ascending
-      segs.push_back({2, 0, residue + gapsum, out, g});
-      gapsum += g; out += g;
-    }
-    out += len;
-    lo = off; ll = len;
-  };
-  for (size_t j = 0; j < ns; j++) {
-    if (!d[j].k) { place(d[j].off, d[j].cl); rec_off[j] = out - d[j].cl; continue; }
-    rec_off[j] = d[j].off;   // (out == off at a stream's first byte: gaps and streams fill the original in order)
-    uint64_t fp = d[j].off;
-    for (uint64_t i = 0; i < d[j].k; i++) {
-      const uint64_t len = rd4le(h + d[j].ppos + 4 * i);
-      place(fp, len);
-      fp += len + 12;
-    }
-  }
-  if (lo + ll < origlen) { segs.push_back({2, 0, residue + gapsum, out, origlen - (lo + ll)}); out += origlen - (lo + ll); }
-  if (out != origlen) return ATZ_E_FORMAT;
-  if (!segs.empty())
-    if (int r = gather_segments(c, d_atz, meta, segs, c->d_rec.as<uint8_t>())) return r;
+  if (!L.gaps.empty())
+    if (int r = gather_segments(c, d_atz, meta, L.gaps, c->d_rec.as<uint8_t>())) return r;
   if (ns) {
     // payloads into an aligned slab (the trial kernels read 256-byte aligned streams)
-    std::vector<uint64_t> loc(ns), addr(ns), len(ns);
-    std::vector<DeflSpec> params(ns);
-    uint64_t tot = 0;
-    for (size_t j = 0; j < ns; j++) { loc[j] = tot; tot += (d[j].il + 255) & ~255ull; }
     if (c->slabs.empty()) c->slabs.emplace_back(new DBuf());
     DBuf& slab = *c->slabs[0];
-    if (int r = slab.reserve(tot + 65536)) return r;
-    segs.clear();
-    for (size_t j = 0; j < ns; j++) {
-      if (d[j].il) segs.push_back({2, 0, d[j].ipos, loc[j], d[j].il});
-      addr[j] = (uint64_t)(uintptr_t)slab.p + loc[j];
-      len[j] = d[j].il;
-      params[j] = DeflSpec::from_desc(d[j].c, d[j].w, d[j].m);
-      if (params[j].window == 8) params[j].window = 9;   // as zlib's deflateInit2 does
-    }
-    if (!segs.empty())
-      if (int r = gather_segments(c, d_atz, meta, segs, slab.as<uint8_t>())) return r;
+    if (int r = slab.reserve(L.slab + 65536)) return r;
+    std::vector<uint64_t> addr(ns), len(ns);
+    for (size_t j = 0; j < ns; j++) { addr[j] = (uint64_t)(uintptr_t)slab.p + L.loc[j]; len[j] = d[j].il; }
+    if (!L.payloads.empty())
+      if (int r = gather_segments(c, d_atz, meta, L.payloads, slab.as<uint8_t>())) return r;
     // Adler-32 of every payload on the device
     if (int r = upload(c, c->d_pos, addr.data(), ns * 8)) return r;
     if (int r = upload(c, c->d_hbase, len.data(), ns * 8)) return r;
@@ -4481,67 +4279,18 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
     KCHECK("k_adler32");
     HIPCHK(hipStreamSynchronize(c->st));
     kcollect(c);
-    int rc2 = deflate_dev(c, addr, len, {}, params,
+    int rc2 = deflate_dev(c, addr, len, {}, L.params,
                           [&](size_t s0, size_t s1, const std::vector<uint64_t>& oa, const std::vector<uint64_t>& ol) -> int {
-      std::vector<Seg> sg;
-      std::vector<uint64_t> pat;
-      std::vector<uint8_t> pval;
-      const uint64_t rb = (uint64_t)(uintptr_t)c->d_rec.p;
-      for (size_t j = s0; j < s1; j++) {
-        const uint64_t L = ol[j - s0], cl = d[j].cl;
-        if (L > cl + 65535) return ATZ_E_REF_ABORT;   // deflate() != Z_STREAM_END in a cl+65535 buffer
-        const uint64_t k = L < cl ? L : cl;
-        if (d[j].k) {
-          // a stitched stream: its bytes go straight to their pieces' file positions -- the output ranges, the
-          // zero extension and (below) each diff position are mapped through the piece prefix sums
-          stitched_ranges(h, d[j], 0, k, [&](uint64_t sp, uint64_t fp, uint64_t len) { sg.push_back({1, 0, oa[j - s0] + sp, fp, len}); });
-          stitched_ranges(h, d[j], k, cl, [&](uint64_t, uint64_t fp, uint64_t len) { sg.push_back({3, 0, 0, fp, len}); });
-        } else {
-          if (k) sg.push_back({1, 0, oa[j - s0], rec_off[j], k});
-          if (cl > k) sg.push_back({3, 0, 0, rec_off[j] + k, cl - k});   // zero-extended buffer
-        }
-        // diff bytes: positions first_diff + prefix sums of the deltas; only those < cl reach the output
-        if (d[j].nd) {
-          const size_t p0 = pat.size();
-          std::vector<uint64_t> pre;   // a stitched stream's pieces: the stream position each starts at
-          for (uint64_t i = 0, sp = 0; i < d[j].k; i++) { pre.push_back(sp); sp += rd4le(h + d[j].ppos + 4 * i); }
-          uint64_t sum = 0;
-          bool increasing = true;
-          for (uint64_t i = 0; i < d[j].nd; i++) {
-            const uint64_t delta = rd8(h + d[j].dpos + 8 * i);
-            const uint64_t at = d[j].fd + delta + sum;
-            sum += delta;
-            if (at < cl) {
-              uint64_t to = rec_off[j] + at;
-              if (d[j].k)   // behind i pieces' framing: i = the last piece that starts at or before `at`
-                to += 12 * (uint64_t)(std::upper_bound(pre.begin(), pre.end(), at) - pre.begin() - 1);
-              if (pat.size() > p0 && rb + to <= pat.back()) increasing = false;
-              pat.push_back(rb + to);
-              pval.push_back(h[d[j].dpos + 8 * d[j].nd + i]);
-            }
-          }
-          if (!increasing) {   // crafted deltas (wrap / zero): the last write to a position wins
-            std::vector<std::pair<uint64_t, size_t>> o;
-            for (size_t q = p0; q < pat.size(); q++) o.push_back({pat[q], q});
-            std::stable_sort(o.begin(), o.end(), [](auto& a, auto& b) { return a.first < b.first; });
-            std::vector<uint64_t> pa;
-            std::vector<uint8_t> pv;
-            for (size_t q = 0; q < o.size(); q++)
-              if (q + 1 == o.size() || o[q + 1].first != o[q].first) { pa.push_back(o[q].first); pv.push_back(pval[o[q].second]); }
-            pat.resize(p0); pval.resize(p0);
-            pat.insert(pat.end(), pa.begin(), pa.end());
-            pval.insert(pval.end(), pv.begin(), pv.end());
-          }
-        }
-      }
-      if (!sg.empty())
-        if (int r = gather_segments(c, d_atz, meta, sg, c->d_rec.as<uint8_t>())) return r;
-      if (!pat.empty()) {
-        if (int r = upload(c, c->d_diffjobs, pat.data(), pat.size() * 8)) return r;
-        if (int r = upload(c, c->d_diffval, pval.data(), pval.size())) return r;
+      RecBatch B;
+      if (int r = plan_batch(h, d, L, origlen, s0, s1, oa, ol, (uint64_t)(uintptr_t)c->d_rec.p, B)) return r;
+      if (!B.segs.empty())
+        if (int r = gather_segments(c, d_atz, meta, B.segs, c->d_rec.as<uint8_t>())) return r;
+      if (!B.pat.empty()) {
+        if (int r = upload(c, c->d_diffjobs, B.pat.data(), B.pat.size() * 8)) return r;
+        if (int r = upload(c, c->d_diffval, B.pval.data(), B.pval.size())) return r;
         kbeg(c, 3);
-        hipLaunchKernelGGL(k_patch, dim3((uint32_t)((pat.size() + 255) / 256)), dim3(256), 0, c->st,
-                           c->d_diffjobs.as<uint64_t>(), c->d_diffval.as<uint8_t>(), (uint64_t)pat.size());
+        hipLaunchKernelGGL(k_patch, dim3((uint32_t)((B.pat.size() + 255) / 256)), dim3(256), 0, c->st,
+                           c->d_diffjobs.as<uint64_t>(), c->d_diffval.as<uint8_t>(), (uint64_t)B.pat.size());
         kend(c);
         KCHECK("k_patch");
         HIPCHK(hipStreamSynchronize(c->st));
@@ -4703,7 +4452,7 @@ static int shard_sweep_impl(atz_ctx* c, const uint8_t* d_file, const uint8_t* h,
   std::vector<uint8_t> meta;
   std::vector<Seg> segs;
   uint64_t out = 0;
-  atz_descriptors(c, ss, meta, segs, out);
+  write_descriptors(n, write_recs(c, ss), meta, segs, out);
   if (int r = c->d_atz.reserve(out + 4096)) return r;
   if (!segs.empty())
     if (int r = gather_segments(c, d_file, meta, segs, c->d_atz.as<uint8_t>())) return r;
@@ -4731,12 +4480,10 @@ static int shard_assemble_impl(atz_ctx* c, const uint8_t* d_file, uint64_t F, co
   if (nr != n_recomp) return ATZ_E_ARG;
   std::vector<uint8_t> meta;
   std::vector<Seg> segs;
-  atz_header(meta, F, n_recomp);
-  segs.push_back({0, 0, 0, 0, meta.size()});
-  uint64_t out = meta.size() + pieces_len;   // the pieces are already in place
-  if (int r = atz_residue(sh.all, flags, F, segs, out)) return r;
+  uint64_t out = write_header(meta, segs, F, n_recomp, 1) + pieces_len;   // the pieces are already in place
+  if (int r = write_residue(sh.all, flags, F, segs, out)) return r;
   if (out > cap) return ATZ_E_ARG;
-  std::memcpy(meta.data() + 4, &out, 8);
+  write_length(meta, out);
   if (int r = gather_segments(c, d_file, meta, segs, d_atz)) return r;
   *atz_len = out;
   return 0;

@@ -67,6 +67,7 @@ struct DeflSpec {
   uint8_t min_version(bool stitched) const {
     return flush ? 6 : gnu ? 5 : stitched ? 4 : raw ? 3 : strategy ? 2 : 1;
   }
+  static constexpr uint8_t MAX_VERSION = 6;   // the highest version a reader accepts (and min_version returns)
 };
 
 // A reader of `version` (1-6) accepts the descriptor bytes (c with its bit 7).  parse_atz's size and layout

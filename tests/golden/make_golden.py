@@ -16,7 +16,6 @@ import hashlib
 import json
 import os
 import shutil
-import struct
 import subprocess
 import sys
 import tempfile
@@ -27,6 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from antiz_amd import datagen  # noqa: E402
 import _libs  # noqa: E402
+import atzfile  # noqa: E402
 
 ZT = "/root/reference/includes, tools, stuff/zlib test/bin/Release"
 ZT_FILES = ["input.bin", "zlibtest_out_c1.bin", "zlibtest_out_2k.bin", "zlibtest_out_c5.bin",
@@ -39,15 +39,8 @@ def sha(b):
 
 def parse_atz(atz):
     """stream descriptors of an ATZ1 file (main.cpp:1031-1063)"""
-    n = struct.unpack_from("<Q", atz, 20)[0]
-    pos, out = 28, []
-    for _ in range(n):
-        off, cl, il = struct.unpack_from("<QQQ", atz, pos)
-        c, w, m = atz[pos + 24], atz[pos + 25], atz[pos + 26]
-        nd = struct.unpack_from("<Q", atz, pos + 27)[0]
-        out.append(dict(offset=off, comp_len=cl, infl_len=il, clevel=c, window=w, memlevel=m, n_diff=nd))
-        pos += (43 + 9 * nd if nd else 35) + il
-    return out
+    return [dict(offset=d["off"], comp_len=d["cl"], infl_len=d["il"], clevel=d["c"], window=d["w"], memlevel=d["m"],
+                 n_diff=d["nd"]) for d in atzfile.parse(atz)[2]]
 
 
 def run_ref(data, opts):

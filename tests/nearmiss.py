@@ -35,6 +35,7 @@ import zlib
 import numpy as np
 
 import _libs
+import atzfile
 from antiz_amd import datagen
 
 Stream = collections.namedtuple("Stream", "offset length family tag data_len pads")
@@ -386,27 +387,9 @@ def flags_kwargs(flags, names=("recomp", "sizediff", "shortcut", "tol", "brute")
 def parse_atz1(atz):
     """The stream table of an ATZ1 file: one dict per recompressed stream with its
     offset, comp_len, c, w, m, n_diff, first_diff and the absolute diff positions and values."""
-    import struct
     assert atz[:4] == b"ATZ\x01"
-    total, _, n = struct.unpack_from("<QQQ", atz, 4)
-    assert total == len(atz)
-    at, out = 28, []
-    for _ in range(n):
-        off, cl, il, c, w, m, nd = struct.unpack_from("<QQQBBBQ", atz, at)
-        at += 35
-        e = dict(offset=off, comp_len=cl, c=c, w=w, m=m, n_diff=nd, first_diff=-1, pos=[], val=b"")
-        if nd:
-            fd = struct.unpack_from("<Q", atz, at)[0]
-            deltas = struct.unpack_from("<%dQ" % nd, atz, at + 8)
-            e["first_diff"], p = fd, fd
-            for d in deltas:
-                p += d
-                e["pos"].append(p)
-            e["val"] = atz[at + 8 + 8 * nd:at + 8 + 9 * nd]
-            at += 8 + 9 * nd
-        at += il
-        out.append(e)
-    return out
+    return [dict(offset=d["off"], comp_len=d["cl"], c=d["c"], w=d["w"], m=d["m"], n_diff=d["nd"], first_diff=d["first_diff"],
+                 pos=d["pos"], val=d["val"]) for d in atzfile.parse(atz)[2]]
 
 
 # ---- the fixture (tests/golden/nearmiss.json) --------------------------------------------------------

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import _libs
+import atzfile
 import zstrat
 
 pytestmark = pytest.mark.gpu
@@ -228,19 +229,9 @@ def build_file(seed=5, strategy_streams=True):
 
 
 def parse_atz(atz):
-    """-> (version, origlen, [dict(off, cl, il, c, w, m, nd, raw)]) of an ATZ1 / ATZ2 file."""
-    assert atz[:3] == b"ATZ"
-    total, origlen, ns = struct.unpack_from("<QQQ", atz, 4)
-    assert total == len(atz)
-    at, out = 28, []
-    for _ in range(ns):
-        off, cl, il = struct.unpack_from("<QQQ", atz, at)
-        c, w, m = atz[at + 24], atz[at + 25], atz[at + 26]
-        nd, = struct.unpack_from("<Q", atz, at + 27)
-        end = at + 35 + (8 + 9 * nd if nd else 0) + il
-        out.append(dict(off=off, cl=cl, il=il, c=c, w=w, m=m, nd=nd, raw=atz[at:end]))
-        at = end
-    return atz[3], origlen, out
+    """-> (version, origlen, [dict(off, cl, il, c, w, m, nd, raw)]) of an ATZ file (atzfile.parse's fields of these names)."""
+    ver, origlen, descs, _ = atzfile.parse(atz)
+    return ver, origlen, [{k: d[k] for k in ("off", "cl", "il", "c", "w", "m", "nd", "raw")} for d in descs]
 
 
 @pytest.fixture(scope="module")

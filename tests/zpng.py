@@ -6,6 +6,8 @@ zlib.decompressobj(); expected deflate bytes come from zstrat (the reference's z
 import struct
 import zlib
 
+import atzfile
+
 SIG = b"\x89PNG\r\n\x1a\n"
 FRAMING = 12   # between two payloads: the chunk's CRC, the next chunk's length, "IDAT"
 
@@ -193,25 +195,10 @@ def descriptor(rec, clevel, window, memlevel, diff_pos=(), diff_val=b""):
 
 
 def parse_atz(atz):
-    """-> (version, origlen, [dict(off, cl, il, c, w, m, nd, raw, pieces)], residue bytes) of an ATZ1..4 file;
-    pieces: a stitched descriptor's lengths, else None."""
-    assert atz[:3] == b"ATZ"
-    total, origlen, ns = struct.unpack_from("<QQQ", atz, 4)
-    assert total == len(atz)
-    at, out = 28, []
-    for _ in range(ns):
-        off, cl, il = struct.unpack_from("<QQQ", atz, at)
-        c, w, m = atz[at + 24], atz[at + 25], atz[at + 26]
-        nd, = struct.unpack_from("<Q", atz, at + 27)
-        end = at + 35 + (8 + 9 * nd if nd else 0) + il
-        pieces = None
-        if atz[3] == 4 and c & 0x80:
-            k, = struct.unpack_from("<I", atz, end)
-            pieces = list(struct.unpack_from("<%dI" % k, atz, end + 4))
-            end += 4 + 4 * k
-        out.append(dict(off=off, cl=cl, il=il, c=c, w=w, m=m, nd=nd, raw=atz[at:end], pieces=pieces))
-        at = end
-    return atz[3], origlen, out, atz[at:]
+    """-> (version, origlen, [dict(off, cl, il, c, w, m, nd, raw, pieces)], residue bytes) of an ATZ file
+    (atzfile.parse's fields of these names); pieces: a stitched descriptor's lengths, else None."""
+    ver, origlen, descs, res = atzfile.parse(atz)
+    return ver, origlen, [{k: d[k] for k in ("off", "cl", "il", "c", "w", "m", "nd", "raw", "pieces")} for d in descs], res
 
 
 def residue(data, ranges):
