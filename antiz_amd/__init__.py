@@ -57,7 +57,7 @@ EXPORTS = ["atz_open", "atz_close", "atz_strerror", "atz_free", "atz_default_opt
            "atz_shard_assemble", "atz_reconstruct_device", "atz_deflate_batch_ex", "atz_set_strategies",
            "atz_set_containers", "atz_container_anchors", "atz_set_stitch", "atz_stitch_anchors",
            "atz_stitch_pieces", "atz_set_probe", "atz_probe_positions", "atz_set_deflaters",
-           "atz_set_segments", "atz_flush_markers", "atz_inflate_segments"]
+           "atz_set_segments", "atz_flush_markers", "atz_inflate_segments", "atz_set_nesting", "atz_nest_stats"]
 
 # zlib's strategy numbers (Z_FIXED, 4, is not supported); a strategy mask has bit k set for strategy k
 STRATEGIES = {"filtered": 1, "huffman": 2, "rle": 3}
@@ -126,6 +126,23 @@ def segments_mask(names):
 
 
 # The clevel byte of a descriptor: stitched << 7 | raw << 6 | strategy << 4 | level (csrc/atz_params.h).
+def nest_depth(text):
+    """ATZ_NEST's text (or an int) -> the nesting depth, 0-4; ValueError on anything else.  Empty text: 0."""
+    if isinstance(text, bool):
+        raise ValueError("nesting depth %r" % (text,))
+    if isinstance(text, int):
+        depth = text
+    else:
+        if text == "":
+            return 0
+        if not (text.isascii() and text.isdigit()):
+            raise ValueError("nesting depth %r is not a decimal number" % (text,))
+        depth = int(text)
+    if not 0 <= depth <= 4:
+        raise ValueError("nesting depth %d (0 to 4)" % depth)
+    return depth
+
+
 def _pack(strategy, level, raw, stitched):
     if raw and stitched:
         raise ValueError("a descriptor is raw or stitched, not both")
@@ -217,6 +234,8 @@ def lib():
         L.atz_flush_markers.argtypes = L.atz_probe_positions.argtypes
         L.atz_inflate_segments.argtypes = [C.c_void_p, C.c_char_p, u64, C.POINTER(u64), C.POINTER(u64), u64,
                                            C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint8)]
+        L.atz_set_nesting.argtypes = [C.c_void_p, C.c_int]
+        L.atz_nest_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(Stats)]
         L.atz_deflate_bound.restype = u64
         L.atz_deflate_bound.argtypes = [u64, C.c_int, C.c_int]
         L.atz_shard_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, u64, C.c_int, C.c_int, C.POINTER(u8p),
@@ -243,7 +262,7 @@ class Context:
 
     def __init__(self, recomp_tresh=128, sizediff_tresh=128, shortcut_len=512, mismatch_tol=2,
                  chunksize=524288, brute_window=False, device=-1, strategies=None, containers=None, stitch=None,
-                 probe=None, deflaters=None, segments=None):
+                 probe=None, deflaters=None, segments=None, nest=None):
         """strategies: names of zlib strategies ("filtered", "rle", "huffman") to try on the streams the
         reference walk leaves unrecorded (an extension, off by default; None reads ATZ_STRATEGIES, a
         comma-separated list, as the CLI does).
@@ -257,7 +276,10 @@ class Context:
         deflaters: "gnu": the raw records' walk (containers, probe) also tries the deflater of GNU gzip and Info-ZIP's
         zip (an extension, off by default; None reads ATZ_DEFLATERS, a comma-separated list, as the CLI does).
         segments: "flush": a stream cut by full-flush points (Z_FULL_FLUSH, pigz -i) is recorded as one raw record per
-        segment (an extension, off by default; None reads ATZ_SEGMENTS, a comma-separated list, as the CLI does)."""
+        segment (an extension, off by default; None reads ATZ_SEGMENTS, a comma-separated list, as the CLI does).
+        nest: a depth 1-4: precompress also runs the whole pipeline, that many levels down, on the payloads of the
+        streams it recorded and writes a nested file, magic "ATN" 1 (an extension, off by default, 0; None reads ATZ_NEST,
+        a decimal depth, as the CLI does)."""
         L = lib()
         self.o = Opts(recomp_tresh, sizediff_tresh, shortcut_len, mismatch_tol, chunksize, int(brute_window), device)
         if strategies is None:
@@ -278,6 +300,9 @@ class Context:
         if segments is None:
             segments = os.environ.get("ATZ_SEGMENTS", "")
         gmask = segments_mask(segments)
+        if nest is None:
+            nest = os.environ.get("ATZ_NEST", "")
+        depth = nest_depth(nest)
         self.h = C.c_void_p()
         _check(L.atz_open(C.byref(self.h), C.byref(self.o)))
         if mask:
@@ -292,6 +317,8 @@ class Context:
             _check(L.atz_set_deflaters(self.h, dmask))
         if gmask:
             _check(L.atz_set_segments(self.h, gmask))
+        if depth:
+            _check(L.atz_set_nesting(self.h, depth))
 
     def close(self):
         if self.h:
@@ -313,6 +340,13 @@ class Context:
         out = C.string_at(p, n.value)
         L.atz_free(p)
         return out, st.as_dict()
+
+    def nest_stats(self, level):
+        """The stats of nesting level `level` (0: this context's own) of the last precompress; AtzError (ATZ_E_ARG) if
+        that level did not run."""
+        st = Stats()
+        _check(lib().atz_nest_stats(self.h, level, C.byref(st)))
+        return st.as_dict()
 
     def precompress_device(self, d_ptr, host_data):
         """Input already resident in HBM (d_ptr: device pointer, e.g. torch tensor.data_ptr())."""

@@ -716,6 +716,16 @@ struct atz_ctx {
   // layout the sweep's threads share: with the mask off the call's stack is exactly what it was)
   ProbeList probe;
   MarkerList marks;   // the segment extension's, likewise
+  // opt-in nesting (atz_set_nesting): with a depth d >= 1 a precompress runs the whole pipeline
+  // again, at depth d - 1, on P -- the recorded streams' payloads, gathered into d_nestp and copied once to
+  // h_nestp -- in a child context on the same device, opened at the first need and closed with this one.  A
+  // reconstruct of a nested file uses the child too, whatever the depth: the inner file's original stays in the
+  // child's d_rec.  nest_ran: the child's precompress completed in this context's last precompress.
+  int nest_depth = 0;
+  atz_ctx* nest_child = nullptr;
+  bool nest_ran = false;
+  DBuf d_nestp;
+  std::vector<uint8_t> h_nestp;
 };
 
 // kind: 0 trial, 1 inflate, 2 chains, 3 other, 4 match tables, 5 GNU-family trial (counted as a trial too)
@@ -4001,6 +4011,100 @@ static bool spec_abort_test() {   // ATZ_SPEC_ABORT_TEST=1 (read per call): with
   return e && *e == '1';
 }
 
+// ---------------------------------------------------------------------------------------------
+// Opt-in nesting (atz_set_nesting)
+static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, uint64_t F, uint64_t* atz_len,
+                           std::vector<StreamState>* ss_out);
+
+// The context's child: same device and options, its own stream, buffers and records
+static int nest_child(atz_ctx* c, atz_ctx** out) {
+  if (!c->nest_child) {
+    std::unique_ptr<atz_ctx> k(new atz_ctx());
+    k->o = c->o;
+    k->o.device = c->dev;
+    k->dev = c->dev;
+    if (hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking) != hipSuccess) return ATZ_E_HIP;
+    c->nest_child = k.release();
+  }
+  *out = c->nest_child;
+  return 0;
+}
+
+static void close_ctx(atz_ctx* c) {
+  if (!c) return;
+  close_ctx(c->nest_child);
+  c->nest_child = nullptr;
+  hipStreamSynchronize(c->st);
+  hipStreamDestroy(c->st);
+  delete c;   // every DBuf member frees its device memory
+}
+
+// While the child runs, the parent's sweep is over: its pipes (their trial, symbol and match-table buffers and
+// streams) and the chunks of its bucket-table and saved-sequence arenas serve the child, and come back with whatever
+// the child added.  (A chunk list only grows at its end, so the owner's position in it stays valid.)
+struct NestLend {
+  atz_ctx *a, *b;
+  NestLend(atz_ctx* a_, atz_ctx* b_) : a(a_), b(b_) { swap(); }
+  ~NestLend() { swap(); }
+  void swap() {
+    std::swap(a->pipes, b->pipes);
+    std::swap(a->chain_arena.chunks, b->chain_arena.chunks);
+    std::swap(a->chain_arena.span, b->chain_arena.span);
+    std::swap(a->rp_arena.chunks, b->rp_arena.chunks);
+    std::swap(a->rp_arena.span, b->rp_arena.span);
+  }
+};
+
+// Phase 4 of a context with a depth, after level 0's passes.  P is gathered from the payloads where they lie, the
+// child precompresses it, and if the child recorded a stream the file is the nested one (nested = true): the
+// stripped outer and the child's file behind the 20 header bytes.  Else nothing is written here and the caller
+// writes the flat file.
+static int nest_write(atz_ctx* c, const uint8_t* d_file, uint64_t F, const std::vector<StreamState>& ss,
+                      uint64_t* atz_len, bool& nested) {
+  nested = false;
+  c->nest_ran = false;
+  auto rec = write_recs(c, ss);
+  std::vector<Seg> psegs;
+  uint64_t plen = 0;
+  if (!plan_payloads(c->recs.size(), rec, psegs, plen) || !plen) return 0;
+  if (int r = c->d_nestp.reserve(plen + 4096)) return r;
+  const std::vector<uint8_t> none(8, 0);
+  if (int r = gather_segments(c, d_file, none, psegs, c->d_nestp.as<uint8_t>())) return r;
+  HIPCHK(hipMemsetAsync(c->d_nestp.as<uint8_t>() + plen, 0, 4096, c->st));   // the slack a file has
+  c->h_nestp.resize(plen);
+  HIPCHK(hipMemcpyAsync(c->h_nestp.data(), c->d_nestp.p, plen, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  atz_ctx* k = nullptr;
+  if (int r = nest_child(c, &k)) return r;
+  k->o = c->o; k->o.device = c->dev;
+  k->strat_mask = c->strat_mask; k->cont_mask = c->cont_mask; k->stitch_mask = c->stitch_mask;
+  k->probe_mask = c->probe_mask; k->seg_mask = c->seg_mask; k->defl_mask = c->defl_mask;
+  k->nest_depth = c->nest_depth - 1;
+  k->nest_ran = false;
+  uint64_t inner_len = 0;
+  int rc;
+  {
+    NestLend lend(c, k);
+    rc = precompress_dev(k, c->d_nestp.as<uint8_t>(), c->h_nestp.data(), plen, &inner_len, nullptr);
+  }
+  if (rc == ATZ_E_REF_ABORT || rc == ATZ_E_REF_UB) return 0;   // the reference itself would have died on P
+  if (rc) return rc;
+  c->nest_ran = true;
+  if (!k->stats.n_recomp) return 0;
+  auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint8_t> meta;
+  std::vector<Seg> segs;
+  uint64_t outer_len = 0, out = 0;
+  if (int r = write_file(c->recs.size(), rec, F, meta, segs, outer_len, true)) return r;
+  if (int r = write_nest(meta, segs, outer_len, (uint64_t)(uintptr_t)k->d_atz.p, inner_len, out)) return r;
+  if (int r = c->d_atz.reserve(out + 4096)) return r;
+  if (int r = gather_segments(c, d_file, meta, segs, c->d_atz.as<uint8_t>())) return r;
+  *atz_len = out;
+  c->stats.write_ms = ms_since(t0);
+  nested = true;
+  return 0;
+}
+
 static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, uint64_t F, uint64_t* atz_len,
                            std::vector<StreamState>* ss_out) {
   auto t0 = std::chrono::steady_clock::now();
@@ -4124,7 +4228,11 @@ static int precompress_dev(atz_ctx* c, const uint8_t* d_file, const uint8_t* h, 
   if (int r = raw_pass(c, d_file, ss)) return r;
   c->infl_off.resize(c->recs.size());
   c->adler.resize(c->recs.size());
-  if (int r = write_impl(c, d_file, F, ss, atz_len)) return r;
+  bool nested = false;
+  if (c->nest_depth)
+    if (int r = nest_write(c, d_file, F, ss, atz_len, nested)) return r;
+  if (!nested)
+    if (int r = write_impl(c, d_file, F, ss, atz_len)) return r;
   c->stats.n_streams = c->recs.size();
   for (auto& s2 : ss) c->stats.n_recomp += s2.recomp;
   c->stats.atz_bytes = *atz_len;
@@ -4246,15 +4354,17 @@ static int deflate_many(atz_ctx* c, const std::vector<std::pair<const uint8_t*, 
 // per stream (doDeflate, main.cpp:976-1003), diff bytes patched (main.cpp:916-926) and the original
 // assembled in c->d_rec by k_gather: residue gaps, the first comp_len bytes of each deflate output
 // (zero-extended, as the reference's buffer is), the tail.
-static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, uint64_t n, uint64_t* out_len) {
+// P: where the payloads lie -- in the file, or (the stripped outer of a nested file) in the inner file's original.
+static int reconstruct_flat(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, uint64_t n, uint64_t* out_len,
+                            const PayloadSrc& P) {
   auto t0 = std::chrono::steady_clock::now();
   std::vector<AtzDesc> d;
   uint64_t origlen = 0, residue = 0;
-  if (int r = parse_atz(h, n, d, origlen, residue)) return r;
+  if (int r = parse_atz(h, n, d, origlen, residue, P.stripped, P.plen)) return r;
   if (int r = c->d_rec.reserve(origlen + 4096)) return r;
   const size_t ns = d.size();
   RecLayout L;
-  if (int r = plan_layout(h, n, d, origlen, residue, L)) return r;
+  if (int r = plan_layout(h, n, d, origlen, residue, L, P)) return r;
   const std::vector<uint8_t> meta(8, 0);
   // residue gaps and the tail are plain copies; the streams' segments come from their batches
   if (!L.gaps.empty())
@@ -4304,6 +4414,30 @@ static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, u
   *out_len = origlen;
   c->stats.total_ms = ms_since(t0);
   return 0;
+}
+
+// A nested file (h at its "ATN" header, accepted by parse_nest): the child rebuilds the inner file's original, P, from
+// d_atz + offset and h + offset, into its d_rec; the outer's layout and batches then run as a flat file's, their
+// payload segments sourced from P where it lies.
+static int reconstruct_dev(atz_ctx* c, const uint8_t* d_atz, const uint8_t* h, uint64_t n, uint64_t* out_len,
+                           bool checked = false) {
+  if (!is_nest(h, n)) return reconstruct_flat(c, d_atz, h, n, out_len, PayloadSrc{});
+  if (!checked) {
+    std::vector<NestLevel> lv;
+    if (int r = parse_nest(h, n, lv)) return r;
+  }
+  const uint64_t outer_len = rd8(h + 12), in = NEST_HEADER + outer_len;
+  atz_ctx* k = nullptr;
+  if (int r = nest_child(c, &k)) return r;
+  k->scan_valid = false; k->shard.stage = 0;
+  uint64_t plen = 0;
+  {
+    NestLend lend(c, k);   // (this context's deflates come after the child's)
+    if (int r = reconstruct_dev(k, d_atz + in, h + in, n - in, &plen, true)) return r;
+  }
+  PayloadSrc P;
+  P.stripped = true; P.pbase = (uint64_t)(uintptr_t)k->d_rec.p; P.plen = plen;
+  return reconstruct_flat(c, d_atz + NEST_HEADER, h + NEST_HEADER, outer_len, out_len, P);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4558,9 +4692,7 @@ int atz_open(atz_ctx_t** ctx, const atz_opts_t* opts) {
 void atz_close(atz_ctx_t* c) {
   if (!c) return;
   try {
-    hipStreamSynchronize(c->st);
-    hipStreamDestroy(c->st);
-    delete c;   // every DBuf member frees its device memory
+    close_ctx(c);   // (and its nesting children)
   } catch (...) {
   }
 }
@@ -4889,6 +5021,24 @@ int atz_set_segments(atz_ctx_t* c, uint32_t mask) {
   return ATZ_OK;
 }
 
+int atz_set_nesting(atz_ctx_t* c, int depth) {
+  if (!c || depth < 0 || depth > 4) return ATZ_E_ARG;
+  c->nest_depth = depth;
+  c->nest_ran = false;
+  return ATZ_OK;
+}
+
+int atz_nest_stats(atz_ctx_t* c, int level, atz_stats_t* stats) {
+  if (!c || !stats || level < 0 || level > 4) return ATZ_E_ARG;
+  const atz_ctx* k = c;
+  for (int l = 0; l < level; l++) {   // level l + 1 ran in level l's last precompress
+    if (!k->nest_depth || !k->nest_ran || !k->nest_child) return ATZ_E_ARG;
+    k = k->nest_child;
+  }
+  *stats = k->stats;
+  return ATZ_OK;
+}
+
 int atz_flush_markers(atz_ctx_t* c, const uint8_t* file, uint64_t len, uint64_t** out, uint64_t* n) {
   return guarded([&]() -> int {
     (void)hipGetLastError();
@@ -4978,7 +5128,7 @@ int atz_shard_scan(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, u
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !blob || !blob_len || world < 1 || rank < 0 || rank >= world) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask || c->seg_mask) return ATZ_E_ARG;   // the extensions have no multi-GPU split
+    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask || c->seg_mask || c->nest_depth) return ATZ_E_ARG;   // the extensions have no multi-GPU split
     dev_mark_call();   // (the peak runs on through atz_shard_sweep, whose stats report it)
     std::vector<uint64_t> b;
     if (int r = shard_scan_impl(c, d_file, h_file, len, rank, world, b)) { c->shard.stage = 0; return r; }
@@ -4996,7 +5146,7 @@ int atz_shard_sweep(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, 
   return guarded([&]() -> int {
     (void)hipGetLastError();
     if (!c || !d_file || !h_file || !piece_len || !recomp_flags || !n_flags || !n_recomp) return ATZ_E_ARG;
-    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask || c->seg_mask) return ATZ_E_ARG;
+    if (c->strat_mask || c->cont_mask || c->stitch_mask || c->probe_mask || c->defl_mask || c->seg_mask || c->nest_depth) return ATZ_E_ARG;
     std::vector<uint8_t> f;
     if (int r = shard_sweep_impl(c, d_file, h_file, len, blobs, blob_lens, world, f, n_recomp)) {
       c->shard.stage = 0;
@@ -5016,7 +5166,7 @@ int atz_shard_sweep(atz_ctx_t* c, const uint8_t* d_file, const uint8_t* h_file, 
 int atz_shard_piece(atz_ctx_t* c, uint8_t* d_dst) {
   return guarded([&]() -> int {
     (void)hipGetLastError();
-    if (!c || c->shard.stage != 2 || (!d_dst && c->shard.piece_len)) return ATZ_E_ARG;
+    if (!c || c->nest_depth || c->shard.stage != 2 || (!d_dst && c->shard.piece_len)) return ATZ_E_ARG;
     if (c->shard.piece_len)
       HIPCHK(hipMemcpyAsync(d_dst, c->d_atz.p, c->shard.piece_len, hipMemcpyDeviceToDevice, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -5029,7 +5179,7 @@ int atz_shard_assemble(atz_ctx_t* c, const uint8_t* d_file, uint64_t len, const 
                        uint64_t* atz_len) {
   return guarded([&]() -> int {
     (void)hipGetLastError();
-    if (!c || !d_file || !atz_len) return ATZ_E_ARG;
+    if (!c || !d_file || !atz_len || c->nest_depth) return ATZ_E_ARG;
     return shard_assemble_impl(c, d_file, len, recomp_flags, n_flags, n_recomp, pieces_len, d_atz, cap, atz_len);
   });
 }

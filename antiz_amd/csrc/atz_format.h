@@ -5,6 +5,10 @@
 //   descriptor: u64 offset, comp_len, infl_len | clevel, window, memLevel | u64 ndiff
 //               [ u64 first_diff | ndiff x u64 delta | ndiff x u8 value ] | infl_len payload bytes
 //               [ u32 k | k x u32 piece length ]      (a stitched descriptor: bit 7 of clevel, version >= 4)
+// A nested file wraps two of them:
+//   "ATN" 1 | u64 length | u64 outer_len | outer (outer_len bytes) | inner (to the end)
+// outer: an ATZ file without its descriptors' payload bytes ("stripped"); inner: the ATZ or ATN file of P, the outer's
+// payloads concatenated in descriptor order.
 // Both plans are lists of k_gather segments (Seg) plus, for reconstruct, k_patch's (address, value) pairs.  The
 // kernels execute them with raw device addresses, so every bound they rely on is checked here: a plan function
 // that would emit a range outside its buffer returns ATZ_E_INTERNAL instead (one comparison per stream or segment).
@@ -38,6 +42,7 @@ inline bool inside(uint64_t off, uint64_t len, uint64_t cap) { return off <= cap
 // Reader
 // (dpos: the deltas, their values behind them; ipos: the payload; k, ppos: a stitched descriptor's piece count and
 // the position of its k u32 piece lengths; k = 0: not stitched)
+// (in a stripped file ipos is the payload's offset in P)
 struct AtzDesc {
   uint64_t off, cl, il, nd, fd, dpos, ipos; uint8_t c, w, m;
   uint64_t k = 0, ppos = 0;
@@ -56,8 +61,11 @@ inline void stitched_ranges(const uint8_t* atz, const AtzDesc& x, uint64_t a, ui
 }
 
 // ATZ parse with the reference's checks (main.cpp:1011-1063); every size field is bounded by the
-// bytes actually left before anything is sized from it (subtraction-only checks: no sum can wrap)
-inline int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, uint64_t& origlen, uint64_t& residue) {
+// bytes actually left before anything is sized from it (subtraction-only checks: no sum can wrap).
+// stripped: the outer file of a nested one -- no payload bytes follow a descriptor's fixed fields and diff list, and
+// payload j is bytes [sum of the infl_len before it, + infl_len) of P, whose plen bytes bound them.
+inline int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, uint64_t& origlen, uint64_t& residue,
+                     bool stripped = false, uint64_t plen = 0) {
   // (the versions and what their descriptors may carry: atz_params.h)
   if (n < 28 || std::memcmp(atz, "ATZ", 3) != 0 || atz[3] < 1 || atz[3] > DeflSpec::MAX_VERSION) return ATZ_E_FORMAT;   // main.cpp:1018-1021
   const int version = atz[3];
@@ -73,6 +81,7 @@ inline int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
   if (nstrms > (n - 28) / 35) return ATZ_E_FORMAT;                       // each descriptor is >= 35 bytes
   d.resize(nstrms);
   uint64_t lastos = 28;                                                    // main.cpp:1031-1063
+  uint64_t pat = 0;                                                        // stripped: the next payload's place in P
   for (uint64_t j = 0; j < nstrms; j++) {
     if (n - lastos < 35) return ATZ_E_FORMAT;
     AtzDesc& x = d[j];
@@ -83,13 +92,18 @@ inline int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
       if (n - lastos < 43) return ATZ_E_FORMAT;
       const uint64_t room = n - lastos - 43;
       if (x.nd > room / 9) return ATZ_E_FORMAT;
-      if (x.il > room - x.nd * 9) return ATZ_E_FORMAT;
+      if (!stripped && x.il > room - x.nd * 9) return ATZ_E_FORMAT;
       x.fd = rd8(atz + lastos + 35); x.dpos = lastos + 43; x.ipos = lastos + 43 + x.nd * 9;
+    } else {
+      if (!stripped && x.il > n - lastos - 35) return ATZ_E_FORMAT;
+      x.fd = 0; x.dpos = 0; x.ipos = lastos + 35;
+    }
+    if (!stripped) {
       lastos = x.ipos + x.il;
     } else {
-      if (x.il > n - lastos - 35) return ATZ_E_FORMAT;
-      x.fd = 0; x.dpos = 0; x.ipos = lastos + 35;
-      lastos = x.ipos + x.il;
+      if (x.il > plen - pat) return ATZ_E_FORMAT;   // (pat <= plen)
+      lastos = x.ipos; x.ipos = pat;
+      pat += x.il;
     }
     // a refusal of the parameters: the clevel byte's before the piece list is read, the other bytes' after it
     const bool ok = valid_desc(version, x.c, x.w, x.m);
@@ -124,6 +138,47 @@ inline int parse_atz(const uint8_t* atz, uint64_t n, std::vector<AtzDesc>& d, ui
   return 0;
 }
 
+// A nested file's levels, outermost first: every one but the last is a stripped outer, the last a complete ATZ file;
+// level k's payloads are level k + 1's original.  pos, len: the level's bytes in the file.
+struct NestLevel {
+  uint64_t pos = 0, len = 0;
+  std::vector<AtzDesc> d;   // positions relative to pos (a stripped level's ipos: in P)
+  uint64_t origlen = 0, residue = 0;
+};
+enum : uint64_t { NEST_HEADER = 20, NEST_MAX_DEPTH = 8 };
+inline bool is_nest(const uint8_t* a, uint64_t n) { return n >= 4 && std::memcmp(a, "ATN", 3) == 0; }
+// ATN parse: the wrappers first (every size by subtraction from the bytes left), then each level with parse_atz,
+// innermost first, since a stripped level's payloads are bounded by the original of the level inside it.
+inline int parse_nest(const uint8_t* a, uint64_t n, std::vector<NestLevel>& lv) {
+  lv.clear();
+  uint64_t at = 0, left = n;
+  while (left >= 4 && std::memcmp(a + at, "ATN", 3) == 0) {
+    if (lv.size() == NEST_MAX_DEPTH) return ATZ_E_FORMAT;
+    if (left < NEST_HEADER + 28 + 28 || a[at + 3] != 1 || rd8(a + at + 4) != left) return ATZ_E_FORMAT;
+    const uint64_t outer = rd8(a + at + 12);
+    if (outer < 28 || outer > left - NEST_HEADER - 28) return ATZ_E_FORMAT;   // the inner file: a header at least
+    NestLevel L;
+    L.pos = at + NEST_HEADER; L.len = outer;
+    lv.push_back(std::move(L));
+    at += NEST_HEADER + outer; left -= NEST_HEADER + outer;
+  }
+  if (lv.empty()) return ATZ_E_FORMAT;
+  NestLevel last;
+  last.pos = at; last.len = left;
+  lv.push_back(std::move(last));
+  for (size_t k = lv.size(); k-- > 0;) {
+    NestLevel& L = lv[k];
+    const bool stripped = k + 1 < lv.size();
+    if (int r = parse_atz(a + L.pos, L.len, L.d, L.origlen, L.residue, stripped, stripped ? lv[k + 1].origlen : 0)) return r;
+    if (!stripped) continue;
+    if (L.d.empty()) return ATZ_E_FORMAT;
+    uint64_t sum = 0;   // (no wrap: every term was bounded by what P had left)
+    for (const AtzDesc& x : L.d) sum += x.il;
+    if (sum != lv[k + 1].origlen) return ATZ_E_FORMAT;
+  }
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Reconstruct plan (ATZreconstructor::reconstructATZ, main.cpp:869-950), in two steps.
 // Layout, once per file: the original is the residue's gaps and tail (plain copies from the ATZ bytes) around the
@@ -136,9 +191,20 @@ struct RecLayout {
   uint64_t slab = 0;               // the slab's size
   std::vector<DeflSpec> params;    // stream j's deflate, window 8 read as 9 (as zlib's deflateInit2 does)
 };
+// Where the payloads lie: in the file at each descriptor's ipos, or (a stripped file's) in P, plen bytes at absolute
+// address pbase
+struct PayloadSrc { bool stripped = false; uint64_t pbase = 0, plen = 0; };
+enum : uint64_t { SEG_SPLIT = 1ull << 20 };   // k_gather gives one wave per segment: long copies are cut to this
+inline void push_split(std::vector<Seg>& segs, Seg g) {
+  while (g.len > SEG_SPLIT) {
+    segs.push_back({g.src, 0, g.src_off, g.dst_off, SEG_SPLIT});
+    g.src_off += SEG_SPLIT; g.dst_off += SEG_SPLIT; g.len -= SEG_SPLIT;
+  }
+  segs.push_back(g);
+}
 // atz[0, n) and (d, origlen, residue) as parse_atz accepted them
 inline int plan_layout(const uint8_t* atz, uint64_t n, const std::vector<AtzDesc>& d, uint64_t origlen,
-                       uint64_t residue, RecLayout& L) {
+                       uint64_t residue, RecLayout& L, const PayloadSrc& P = PayloadSrc{}) {
   const size_t ns = d.size();
   L = RecLayout{};
   L.rec_off.resize(ns); L.loc.resize(ns); L.params.resize(ns);
@@ -173,9 +239,10 @@ inline int plan_layout(const uint8_t* atz, uint64_t n, const std::vector<AtzDesc
   if (!ok) return ATZ_E_INTERNAL;
   if (out != origlen) return ATZ_E_FORMAT;
   for (size_t j = 0; j < ns; j++) {
-    if (!inside(d[j].ipos, d[j].il, n)) return ATZ_E_INTERNAL;
+    if (!inside(d[j].ipos, d[j].il, P.stripped ? P.plen : n)) return ATZ_E_INTERNAL;
     L.loc[j] = L.slab; L.slab += (d[j].il + 255) & ~255ull;
-    if (d[j].il) L.payloads.push_back({SEG_FILE, 0, d[j].ipos, L.loc[j], d[j].il});
+    if (d[j].il && !P.stripped) L.payloads.push_back({SEG_FILE, 0, d[j].ipos, L.loc[j], d[j].il});
+    if (d[j].il && P.stripped) push_split(L.payloads, {SEG_ADDR, 0, P.pbase + d[j].ipos, L.loc[j], d[j].il});
     L.params[j] = DeflSpec::from_desc(d[j].c, d[j].w, d[j].m);
     if (L.params[j].window == 8) L.params[j].window = 9;
   }
@@ -283,8 +350,10 @@ inline void write_length(std::vector<uint8_t>& meta, uint64_t out) { std::memcpy
 
 // Stream descriptors + inflated payloads of the recompressed streams, in record order
 // (writeStreamdesc, main.cpp:805-831): metadata bytes into `meta`, copy segments into `segs`.
+// stripped: without the payload bytes (a nested file's outer)
 template <class Get>
-inline void write_descriptors(size_t n, Get rec, std::vector<uint8_t>& meta, std::vector<Seg>& segs, uint64_t& out) {
+inline void write_descriptors(size_t n, Get rec, std::vector<uint8_t>& meta, std::vector<Seg>& segs, uint64_t& out,
+                              bool stripped = false) {
   segs.reserve(segs.size() + 2 * n + 8);
   for (size_t s = 0; s < n; s++) {
     const WriteRec r = rec(s);
@@ -301,8 +370,10 @@ inline void write_descriptors(size_t n, Get rec, std::vector<uint8_t>& meta, std
     }
     segs.push_back({SEG_META, 0, m0, out, meta.size() - m0});
     out += meta.size() - m0;
-    segs.push_back({SEG_ADDR, 0, r.payload, out, r.infl_len});
-    out += r.infl_len;
+    if (!stripped) {
+      segs.push_back({SEG_ADDR, 0, r.payload, out, r.infl_len});
+      out += r.infl_len;
+    }
     if (r.k) {   // u32 k, k x u32 piece lengths (piece i starts at offset + sum_{j<i} (len_j + 12))
       const size_t m1 = meta.size();
       put4(meta, r.k);
@@ -340,7 +411,8 @@ inline int write_residue(const std::vector<std::pair<uint64_t, uint64_t>>& rec, 
 // per piece: the framing between them is residue); out: the ATZ's length.  The version is the lowest whose reader
 // accepts every recorded stream: ATZ1 unless one needs more.
 template <class Get>
-inline int write_file(size_t n, Get rec, uint64_t F, std::vector<uint8_t>& meta, std::vector<Seg>& segs, uint64_t& out) {
+inline int write_file(size_t n, Get rec, uint64_t F, std::vector<uint8_t>& meta, std::vector<Seg>& segs, uint64_t& out,
+                      bool stripped = false) {
   uint64_t nrec = 0;
   size_t npieces = 0;
   uint8_t version = 1;
@@ -362,9 +434,45 @@ inline int write_file(size_t n, Get rec, uint64_t F, std::vector<uint8_t>& meta,
   }
   meta.reserve(28 + nrec * 43 + 64);
   out = write_header(meta, segs, F, nrec, version);
-  write_descriptors(n, rec, meta, segs, out);
+  write_descriptors(n, rec, meta, segs, out, stripped);
   if (int r = write_residue(range, rc.data(), F, segs, out)) return r;
   write_length(meta, out);
+  return 0;
+}
+
+// P of the records: the recorded streams' payloads, concatenated in descriptor order with no padding; segs gather
+// them (absolute addresses) to offsets of P, plen its length; -> the number of recorded streams
+template <class Get>
+inline uint64_t plan_payloads(size_t n, Get rec, std::vector<Seg>& segs, uint64_t& plen) {
+  uint64_t nrec = 0;
+  plen = 0;
+  for (size_t s = 0; s < n; s++) {
+    const WriteRec r = rec(s);
+    if (!r.recomp) continue;
+    nrec++;
+    if (r.infl_len) push_split(segs, {SEG_ADDR, 0, r.payload, plen, r.infl_len});
+    plen += r.infl_len;
+  }
+  return nrec;
+}
+
+// The nested file of a stripped outer (meta, segs and outer_len as write_file left them) and the inner file, inner_len
+// bytes at absolute address inner: the outer's segments move behind the 20 header bytes, the inner file follows them.
+inline int write_nest(std::vector<uint8_t>& meta, std::vector<Seg>& segs, uint64_t outer_len, uint64_t inner,
+                      uint64_t inner_len, uint64_t& out) {
+  const uint64_t top = ~0ull - NEST_HEADER;
+  if (outer_len > top || inner_len > top - outer_len) return ATZ_E_INTERNAL;
+  for (Seg& g : segs) {
+    if (!inside(g.dst_off, g.len, outer_len)) return ATZ_E_INTERNAL;
+    g.dst_off += NEST_HEADER;
+  }
+  out = NEST_HEADER + outer_len + inner_len;
+  const size_t m0 = meta.size();
+  const uint8_t h[4] = {'A', 'T', 'N', 1};
+  meta.insert(meta.end(), h, h + 4);
+  put8(meta, out); put8(meta, outer_len);
+  segs.push_back({SEG_META, 0, m0, 0, NEST_HEADER});
+  if (inner_len) push_split(segs, {SEG_ADDR, 0, inner, NEST_HEADER + outer_len, inner_len});
   return 0;
 }
 

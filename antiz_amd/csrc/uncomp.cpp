@@ -422,7 +422,9 @@ int main(int argc, char* argv[]) {
     // ATZ_CONTAINERS; same layout; "ATZ\4": of the stitch extension, ATZ_STITCH, whose stitched descriptors carry a
     // piece list; "ATZ\5": of the deflater extension, ATZ_DEFLATERS, version 4's layout; "ATZ\6": of the segment
     // extension, ATZ_SEGMENTS, likewise)
-    if (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 6) {
+    // ("ATN\1": a nested file, ATZ_NEST below: 20 header bytes, a stripped ATZ file, the ATZ or ATN file of its payloads)
+    const bool nest = az.size() >= 4 && std::memcmp(az.data(), "ATN\1", 4) == 0;
+    if (!nest && (az.size() < 4 || std::memcmp(az.data(), "ATZ", 3) != 0 || az[3] < 1 || az[3] > 6)) {
       std::cout << "Invalid file: ATZ1 header not found" << std::endl;
       return -2;
     }
@@ -433,7 +435,7 @@ int main(int argc, char* argv[]) {
       return -3;
     }
     uint64_t orig = 0;
-    if (az.size() >= 20) std::memcpy(&orig, az.data() + 12, 8);
+    if (az.size() >= (nest ? 40u : 20u)) std::memcpy(&orig, az.data() + (nest ? 32 : 12), 8);   // (nested: the outer's)
     std::cout << "ATZ file size: " << az.size() << std::endl;
     std::cout << "Original file size: " << orig << std::endl;
     if (open_ctx()) return -1;
@@ -465,6 +467,17 @@ int main(int argc, char* argv[]) {
   // announces (atz_set_probe)
   // ATZ_DEFLATERS: the raw records' walk also tries the deflater of GNU gzip and Info-ZIP's zip (atz_set_deflaters)
   // ATZ_SEGMENTS: streams cut by full-flush points are recorded segment by segment (atz_set_segments)
+  // ATZ_NEST: a decimal depth 1-4: also precompress the recorded streams' payloads, that many levels down, and write
+  // a nested file (atz_set_nesting)
+  int nest_depth = 0;
+  if (const char* e = std::getenv("ATZ_NEST")) {
+    const std::string t(e);
+    if (t.find_first_not_of("0123456789") != std::string::npos || t.size() > 9 || (!t.empty() && std::stoi(t) > 4)) {
+      std::cerr << "Error Encountered: " << "ATZ_NEST: not a depth from 0 to 4: " << t << std::endl;
+      return done(1);
+    }
+    nest_depth = t.empty() ? 0 : std::stoi(t);
+  }
   uint32_t strategies = 0, containers = 0, stitch = 0, probe = 0, deflaters = 0, segments = 0;
   if (!env_mask("ATZ_STRATEGIES", {{"filtered", 1u << 1}, {"huffman", 1u << 2}, {"rle", 1u << 3}}, "strategy", strategies) ||
       !env_mask("ATZ_CONTAINERS", {{"zip", 1u << 0}, {"gzip", 1u << 1}}, "container", containers) ||
@@ -480,6 +493,7 @@ int main(int argc, char* argv[]) {
   if (containers && atz_set_containers(ctx, containers) != 0) return done(255);
   if (stitch && atz_set_stitch(ctx, stitch) != 0) return done(255);
   if (probe && atz_set_probe(ctx, probe) != 0) return done(255);
+  if (nest_depth && atz_set_nesting(ctx, nest_depth) != 0) return done(255);
   uint8_t* atz = nullptr;
   uint64_t al = 0;
   atz_stats_t st;

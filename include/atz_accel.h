@@ -23,6 +23,8 @@
  *   atz_set_probe       raw deflate streams that nothing announces ("ATZ\3"),
  *   atz_set_deflaters   raw bodies written by GNU gzip's and Info-ZIP's deflater, not zlib's ("ATZ\5"),
  *   atz_set_segments    streams cut by full-flush points, one raw record per segment ("ATZ\6")
+ * and one that runs the whole pipeline again on what they recorded:
+ *   atz_set_nesting     the streams inside the recorded streams' payloads, a nested file ("ATN\1")
  */
 #ifndef ATZ_ACCEL_H
 #define ATZ_ACCEL_H
@@ -133,7 +135,8 @@ int atz_scan(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, atz_cand_t **out
 int atz_sweep(atz_ctx_t *ctx, const atz_cand_t *cands, uint64_t n, atz_result_t *res,
               uint64_t **diff_off, uint8_t **diff_val, uint64_t *n_diffs);
 
-/* Whole precompress of a host buffer: *atz (atz_free) receives the ATZ1 bytes. */
+/* Whole precompress of a host buffer: *atz (atz_free) receives the ATZ1 bytes (a nested file's, "ATN\1", under
+ * atz_set_nesting). */
 int atz_precompress(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint8_t **atz, uint64_t *atz_len,
                     atz_stats_t *stats);
 
@@ -144,7 +147,7 @@ int atz_precompress(atz_ctx_t *ctx, const uint8_t *file, uint64_t len, uint8_t *
 int atz_precompress_device(atz_ctx_t *ctx, const uint8_t *d_file, const uint8_t *h_file, uint64_t len,
                            const uint8_t **d_atz, uint64_t *atz_len, atz_stats_t *stats);
 
-/* -r: rebuild the original from ATZ1 bytes. *out (atz_free). */
+/* -r: rebuild the original from ATZ1 bytes (or a nested file's, atz_set_nesting). *out (atz_free). */
 int atz_reconstruct(atz_ctx_t *ctx, const uint8_t *atz, uint64_t len, uint8_t **out, uint64_t *out_len);
 
 /* -r with the ATZ1 bytes resident in HBM (d_atz, >= 4096 bytes of slack; h_atz: host copy for the
@@ -276,6 +279,32 @@ int atz_set_deflaters(atz_ctx_t *ctx, uint32_t mask);
  * word asks for a flush-terminated body: only with bit 28, without bit 29, strategy 0 and windows 9-15 (else
  * ATZ_E_ARG).  The atz_shard_* calls return ATZ_E_ARG on a context with a mask. */
 int atz_set_segments(atz_ctx_t *ctx, uint32_t mask);
+
+/* Opt-in nesting (an extension: the reference stops one level down -- a recorded stream's inflated payload goes
+ * into the file as opaque bytes, so the streams inside a .tar.gz's tar, a JAR in a WAR entry or a PDF object stream
+ * stay compressed).  depth 0, the default, is off: no code of the extension runs and every output is what a context
+ * without it writes; depth 1-4 is accepted, anything else is ATZ_E_ARG.  With a depth d >= 1, atz_precompress* run
+ * level 0 as ever; if it recorded a stream, P -- the recorded streams' payloads, concatenated in descriptor order with
+ * no padding, gathered on the device and copied once to the host -- is precompressed as if it were a file, with the
+ * same options, the same six masks and depth d - 1, in a child context on the same device that this context owns,
+ * opens at the first need, keeps and closes with itself.  If the child recorded a stream, the output is a nested file:
+ *   "ATN" 1 | u64 length (whole file) | u64 outer_len | outer (outer_len bytes) | inner (to the end)
+ * outer: the ATZ file (version 1-6, its own length field = outer_len, at least one descriptor) without every
+ * descriptor's infl_len payload bytes -- a stitched descriptor's piece list then directly follows its diff list or
+ * fixed fields; inner: the child's file (ATZ 1-6 or ATN), whose length field is what is left of the file and whose
+ * origlen is the sum of the outer's infl_len; payload j of the outer is bytes [sum_{i<j} il_i, + il_j) of the inner's
+ * original.  If the child recorded none, or P is empty, or the child returned ATZ_E_REF_ABORT or ATZ_E_REF_UB (the
+ * reference itself would have died on P), the output is byte for byte what depth 0 writes; any other error of the
+ * child fails the call.  *stats is level 0's but for atz_bytes and total_ms, which cover the whole file and call.
+ * atz_reconstruct* read a nested file on any context, whatever its depth (at most 8 levels: deeper is
+ * ATZ_E_FORMAT): the child rebuilds the inner file's original in HBM and the outer's payloads are read from there.
+ * atz_scan and atz_sweep are level 0 only and unchanged.  The atz_shard_* calls return ATZ_E_ARG on a context
+ * with a depth. */
+int atz_set_nesting(atz_ctx_t *ctx, int depth);
+
+/* The stats of level `level` (0: this context's own, 1: its child's, ...) of the last atz_precompress* on ctx;
+ * ATZ_E_ARG if that level did not run in it (no depth, no recorded stream or an empty P one level up, a failed child). */
+int atz_nest_stats(atz_ctx_t *ctx, int level, atz_stats_t *stats);
 
 /* The marker kernel's list for a host buffer (parity/debug): *out (atz_free) receives the *n positions q with
  * q + 4 <= len and bytes q..q+3 = 00 00 FF FF, ascending. */
