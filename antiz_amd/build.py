@@ -32,7 +32,7 @@ def _run(cmd):
 def build(force=False, verbose=False):
     os.makedirs(OUT, exist_ok=True)
     srcs = [os.path.join(CSRC, f) for f in ("atz_accel.cpp", "k_inflate.hip", "k_deflate.hip", "atz_device.h", "atz_params.h",
-                                             "atz_format.h")]
+                                             "atz_format.h", "atz_scanext.h")]
     srcs.append(os.path.join(os.path.dirname(HERE), "include", "atz_accel.h"))
     if force or _newer(LIB, srcs):
         cmd = [HIPCC, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-shared", "-x", "hip",

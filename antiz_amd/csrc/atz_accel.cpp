@@ -44,6 +44,7 @@
 #include "../../include/atz_accel.h"
 #include "atz_params.h"
 #include "atz_format.h"
+#include "atz_scanext.h"
 
 using namespace atz;
 
@@ -348,22 +349,7 @@ struct PinBuf {            // pinned host buffer that kernels write directly
   template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-struct Rec {
-  uint64_t offset, comp_len, infl_len;
-  int type;
-  uint32_t flags;
-  uint64_t arena_off = ~0ull;   // scan output kept in the arena (complete), else ~0
-  bool noshort = false;         // k_inflate's INF_HINT_NOSHORT (the multi-GPU split's cost estimate)
-  uint8_t mhint = 0;            // k_inflate's first-block memLevel (0: none; whole match tables for it)
-  // a stitched record (the stitch extension): its comp_len stream bytes lie contiguous at
-  // this offset of the context's stitch buffer and in the file as pieces [p0, p0 + pk) of st_off / st_len,
-  // 12 framing bytes between two pieces; offset is the first piece's.  ~0: an ordinary record
-  uint64_t stitch = ~0ull;
-  uint32_t p0 = 0, pk = 0;
-  // the file range the record occupies: a stitched one's hull includes the framing between its pieces
-  uint64_t hull() const { return comp_len + (stitch != ~0ull ? 12ull * (pk - 1) : 0); }
-};
-
+// (Rec, a record of the scan: atz_scanext.h)
 struct StreamState {
   // sweep
   const std::vector<uint32_t>* list = nullptr;   // packed (c<<16)|(w<<8)|m: the header type's shared list
@@ -430,15 +416,6 @@ void make_tables(DeflTables& T) {
   auto rev = [](uint32_t v, int l) { uint32_t r = 0; for (int i = 0; i < l; i++) { r = (r << 1) | (v & 1); v >>= 1; } return r; };
   for (int n = 0; n < 288; n++) T.st_lcode[n] = (uint16_t)rev(next[T.st_llen[n]]++, T.st_llen[n]);
   for (int n = 0; n < 30; n++) { T.st_dlen[n] = 5; T.st_dcode[n] = (uint16_t)rev((uint32_t)n, 5); }
-}
-
-int header_type_host(unsigned b0, unsigned b1) {
-  static const uint16_t H[24] = {0x2815, 0x2853, 0x2891, 0x28cf, 0x3811, 0x384f, 0x388d, 0x38cb,
-                                 0x480d, 0x484b, 0x4889, 0x48c7, 0x5809, 0x5847, 0x5885, 0x58c3,
-                                 0x6805, 0x6843, 0x6881, 0x68de, 0x7801, 0x785e, 0x789c, 0x78da};
-  unsigned h = (b0 << 8) | b1;
-  for (int t = 0; t < 24; t++) if (H[t] == h) return t;
-  return -1;
 }
 
 // Stream bytes are addressed by absolute device addresses (infl_off / StreamDev.infl_off /
@@ -829,8 +806,6 @@ struct Chunk {
   uint8_t b0;     // buffer[0]
   bool b0_file;   // buffer[0] == file[co] (buffer is contiguous file data)
 };
-
-static constexpr uint64_t ARENA_SLOT = 65536;   // arena slot per scan candidate (longer outputs are re-inflated)
 
 static int timing_level() {   // ATZ_TIMING=1: phase timings, 2: + per-round sweep timeline
   static const int v = [] { const char* e = std::getenv("ATZ_TIMING"); return (int)(e ? std::atoi(e) : 0); }();
@@ -1345,17 +1320,10 @@ static int scan_piece(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, ScanS
 }
 
 // ---------------------------------------------------------------------------------------------
-// Opt-in container anchors (atz_set_containers).  ZIP entries and gzip members hold
-// raw deflate bodies, which no zlib header announces.  k_anchors_ordered lists the fixed headers of both
-// containers in file order; the host parses their variable parts; one raw k_inflate launch decodes the
-// bodies; what the container's own size fields confirm becomes a record of type 24 + hint, merged into
-// the reference's records (which are made first and never change).
-struct RawCand {
-  uint64_t p, d, limit;   // anchor, first body byte, bytes offered to the decoder
-  int kind, hint;         // 0 ZIP / 1 gzip; 0 none, 1 fast, 2 max
-  bool know_c, know_u;    // ZIP: the header states the compressed / the uncompressed size
-  uint64_t csize, usize;
-};
+// The scan's opt-in extensions: containers, stitching, probe, flush segments.  Their
+// rules -- what a list kernel's positions make of jobs, what the jobs' results make of records -- are
+// atz_scanext.h's, which alone reads the host copy of the file; here are the list kernels' launches and, per
+// extension, a merge that runs the jobs between the header's job step and its accept step.
 
 // An ordered list kernel's two passes over the file (count pass, host prefix over the blocks, write pass):
 // launch(nb, seg, cnt, base, out, write) starts one pass of `name`; *kernel_ms: both passes' device time.
@@ -1421,188 +1389,13 @@ static int anchors_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint32_t m
   return 0;
 }
 
-static uint32_t rd2(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-static uint32_t rd4(const uint8_t* p) { return rd2(p) | (rd2(p + 2) << 16); }
-
-// The variable part of each anchor's header, from the host copy: where the body starts, how many bytes
-// the decoder may read, the level hint the container carries.  An anchor whose header runs past the end
-// of the file, or that leaves no byte for a body, is dropped.
-static void raw_candidates(const uint8_t* h, uint64_t n, const std::vector<uint64_t>& anchors, std::vector<RawCand>& out) {
-  out.clear();
-  for (const uint64_t a : anchors) {
-    RawCand r{};
-    r.p = a >> 5; r.kind = (int)(a & 31);
-    if (r.kind > 1) continue;   // an IDAT anchor of the same pass (the stitch extension)
-    const uint8_t* q = h + r.p;
-    if (r.kind == 0) {
-      const uint32_t flag = rd2(q + 6);
-      r.csize = rd4(q + 18); r.usize = rd4(q + 22);
-      r.d = r.p + 30 + rd2(q + 26) + rd2(q + 28);
-      if (r.d >= n) continue;
-      const bool dd = flag & 8;   // sizes follow the body in a data descriptor
-      r.know_c = !dd && r.csize != 0 && r.csize != 0xffffffffu;
-      r.know_u = !dd && r.usize != 0xffffffffu;
-      if (r.know_c && r.csize > n - r.d) continue;
-      r.limit = r.know_c ? r.csize : n - r.d;
-      const uint32_t lv = (flag >> 1) & 3;   // general purpose bits 2-1: 01 maximum, 10 fast, 11 super fast
-      r.hint = lv == 1 ? 2 : lv >= 2 ? 1 : 0;
-    } else {
-      const uint32_t flg = q[3], xfl = q[8];
-      uint64_t at = r.p + 10;
-      bool ok = true;
-      if (flg & 4) {   // FEXTRA
-        if (at + 2 > n) continue;
-        at += 2 + rd2(h + at);
-        ok = at <= n;
-      }
-      for (uint32_t bit = 8; ok && bit <= 16; bit <<= 1)   // FNAME, FCOMMENT: zero-terminated
-        if (flg & bit) {
-          while (at < n && h[at]) at++;
-          ok = at < n;
-          at++;
-        }
-      if (ok && (flg & 2)) { at += 2; ok = at <= n; }   // FHCRC
-      if (!ok || at + 8 >= n) continue;   // (the trailer's 8 bytes follow the body)
-      r.d = at;
-      r.limit = n - at - 8;
-      r.hint = xfl == 2 ? 2 : xfl == 4 ? 1 : 0;
-    }
-    out.push_back(r);
-  }
-}
-
-// A record of ref (in file order, disjoint) meets the file range [lo, hi): only the last one that starts below
-// hi can.  (raw_merge used to compare comp_len, not hull(): no stitched record exists when it runs, so the
-// two are equal there.)
-static bool meets_earlier(const std::vector<Rec>& ref, uint64_t lo, uint64_t hi) {
-  const auto it = std::lower_bound(ref.begin(), ref.end(), hi, [](const Rec& x, uint64_t v) { return x.offset < v; });
-  return it != ref.begin() && (it - 1)->offset + (it - 1)->hull() > lo;
-}
-// The new records (ascending offsets, disjoint, meeting no record of c->recs) take their places in c->recs, which
-// keeps its capacity (the sweep's tables are sized for it).
-static int splice_records(atz_ctx* c, const std::vector<Rec>& add) {
-  if (add.empty()) return 0;
-  const std::vector<Rec>& ref = c->recs;
-  std::vector<Rec> merged;
-  merged.reserve(ref.size() + add.size());
-  size_t i = 0;
-  for (const Rec& e : add) {
-    while (i < ref.size() && ref[i].offset < e.offset) merged.push_back(ref[i++]);
-    merged.push_back(e);
-  }
-  while (i < ref.size()) merged.push_back(ref[i++]);
-  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
-  c->recs.assign(merged.begin(), merged.end());
-  return 0;
-}
-
-// The raw records of the file merged into c->recs (the reference's, complete): candidates decoded (outputs
-// kept in the scan's arena, behind the reference candidates'; fresh_arena: the scan ran no job), accepted
-// by the container's own fields, dropped where they meet a reference record, taken greedily in ascending
-// offset.  c->recs keeps its capacity (the sweep's tables are sized for it).
-static int raw_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t arena_cap, bool fresh_arena,
-                     const std::vector<RawCand>& cands) {
-  if (cands.empty()) return 0;
-  auto tm_ = std::chrono::steady_clock::now();
-  std::vector<InfJob> jobs(cands.size());
-  for (size_t k = 0; k < cands.size(); k++) jobs[k] = {cands[k].d, cands[k].limit, ARENA_OUT, ARENA_SLOT};
-  std::vector<InfRes> res;
-  if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, arena_cap, false, fresh_arena, true)) return r;
-  std::vector<std::pair<Rec, uint64_t>> acc;   // (record, anchor position)
-  for (size_t k = 0; k < cands.size(); k++) {
-    const RawCand& a = cands[k];
-    const InfRes& r = res[k];
-    if (r.status != INF_END || r.produced < 1 || r.produced >= (1ull << 31)) continue;
-    if (a.kind == 0) {
-      if (a.know_c && r.consumed != a.csize) continue;
-      if (a.know_u && r.produced != a.usize) continue;
-    } else if (rd4(h + a.d + r.consumed + 4) != (uint32_t)r.produced) {   // ISIZE
-      continue;
-    }
-    // a reference record that meets [d, d + consumed): the raw one is dropped
-    if (meets_earlier(c->recs, a.d, a.d + r.consumed)) continue;
-    Rec rec{a.d, r.consumed, r.produced, 24 + a.hint, 0, r.arena_off};
-    acc.push_back({rec, a.p});
-  }
-  std::stable_sort(acc.begin(), acc.end(), [](const auto& x, const auto& y) {
-    return x.first.offset != y.first.offset ? x.first.offset < y.first.offset : x.second < y.second;
-  });
-  std::vector<Rec> kept;
-  uint64_t end = 0;
-  for (const auto& e : acc) {
-    if (e.first.offset < end) continue;   // starts inside the raw record kept before it
-    end = e.first.offset + e.first.comp_len;
-    kept.push_back(e.first);
-  }
-  if (int r = splice_records(c, kept)) return r;
-  TMARK("scan: raw candidates");
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Opt-in stitching (atz_set_stitch).  A PNG writer cuts one zlib stream into IDAT chunks:
-// every few KiB of it are followed by 12 framing bytes (the chunk's CRC, the next chunk's length, "IDAT"),
-// at which the scan's decode fails.  k_anchors_ordered (kind 2) lists the IDAT type fields in file order;
-// the host links consecutive chunks into chains; k_gather copies each chain's payloads into one contiguous
-// run of the stitch buffer; one k_inflate launch decodes the runs; a stream that ends, crosses a chunk
-// boundary and meets no record made before becomes a record whose original bytes are the stitched copy.
-struct StitchCand {
-  uint64_t at, total;   // the chain's run in the stitch buffer (256-byte aligned), its payload bytes
-  uint32_t p0, pk;      // its pieces in StitchPlan::off / len (the first and the last are not empty)
-  int type;             // header type 0..23 of the run's first two bytes
-};
-struct StitchPlan {
-  std::vector<StitchCand> cands;
-  std::vector<uint64_t> off, len;   // file offset and length of every candidate's payloads
-  uint64_t bytes = 0;               // the stitch buffer's size (without its slack)
-};
-
 // k_anchors_ordered's mask for the context's extensions: the container kinds and, for a stitch mask, kind 2
 static uint32_t ext_anchor_mask(const atz_ctx* c) { return c->cont_mask | ((c->stitch_mask & 1u) ? 4u : 0u); }
-
-static uint64_t be4(const uint8_t* p) { return ((uint64_t)p[0] << 24) | ((uint64_t)p[1] << 16) | ((uint64_t)p[2] << 8) | p[3]; }
-
-// Chains and candidates from the kernel's anchors (position << 5 | 2 among them, ascending) and the host
-// copy.  A cursor walks the file: an anchor below it belongs to no chain; from an anchor a at or past it the
-// chain follows a' = a + L + 12 while a' is an anchor, and the cursor moves to the end of the last chunk's
-// CRC.  So chains are disjoint.  A chain without its leading empty chunks is a candidate if two chunks or
-// more remain and its payloads start with one of the 24 zlib headers (the two bytes may lie in two chunks).
-static void stitch_candidates(const uint8_t* h, const std::vector<uint64_t>& anchors, StitchPlan& P) {
-  P = StitchPlan{};
-  std::vector<uint64_t> A;
-  for (const uint64_t a : anchors)
-    if ((a & 31) == 2) A.push_back(a >> 5);
-  uint64_t cursor = 0;
-  std::vector<std::pair<uint64_t, uint64_t>> ch;   // (payload offset, length)
-  for (size_t i = 0; i < A.size(); i++) {
-    if (A[i] < cursor) continue;
-    ch.clear();
-    uint64_t a = A[i];
-    size_t j = i;
-    for (;;) {
-      const uint64_t L = be4(h + a - 4);
-      ch.push_back({a + 4, L});
-      cursor = a + 8 + L;
-      j = (size_t)(std::lower_bound(A.begin() + j + 1, A.end(), a + L + 12) - A.begin());
-      if (j == A.size() || A[j] != a + L + 12) break;
-      a = A[j];
-    }
-    size_t q = 0;
-    while (q < ch.size() && ch[q].second == 0) q++;
-    if (ch.size() - q < 2) continue;
-    unsigned hb[2] = {0, 0};
-    uint64_t total = 0;
-    for (size_t k = q; k < ch.size(); k++) {
-      for (uint64_t b = 0; b < ch[k].second && total + b < 2; b++) hb[total + b] = h[ch[k].first + b];
-      total += ch[k].second;
-    }
-    const int type = total >= 2 ? header_type_host(hb[0], hb[1]) : -1;
-    if (type < 0) continue;
-    StitchCand cd{P.bytes, total, (uint32_t)P.off.size(), (uint32_t)(ch.size() - q), type};
-    for (size_t k = q; k < ch.size(); k++) { P.off.push_back(ch[k].first); P.len.push_back(ch[k].second); }
-    P.cands.push_back(cd);
-    P.bytes += (total + 255) & ~255ull;
-  }
+static int probe_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, ProbeList& P) {
+  return positions_dev(c, d_file, F, k_probe_ordered, "k_probe_ordered", P);
+}
+static int markers_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, MarkerList& M) {
+  return positions_dev(c, d_file, F, k_marker_ordered, "k_marker_ordered", M);
 }
 
 // k_gather of the segments into dst (device): metadata, resident payloads, file ranges
@@ -1622,27 +1415,34 @@ static int gather_segments(atz_ctx* c, const uint8_t* d_file, const std::vector<
   return 0;
 }
 
-// The stitched records of the file merged into c->recs (the reference's and the raw ones, complete, in file
-// order).  The stitch buffer holds every candidate's run; the chains are disjoint, so the payload bytes
-// gathered never exceed the file's size F, and with each run rounded up to 256 bytes the buffer is at most
-// F + 256 * candidates bytes, plus the 4 KiB of zero slack that d_file has (the kernels read past an end).
-// Outputs go to the scan's arena behind the earlier candidates' (fresh_arena: no job ran before).
+// The merges below add an extension's records to c->recs (every record made before, complete, in file order),
+// which keeps its capacity (the sweep's tables are sized for it).  The decoded outputs go to the scan's arena,
+// behind the earlier candidates' (fresh_arena: no job ran before).
+static int raw_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t arena_cap, bool fresh_arena,
+                     const std::vector<RawCand>& cands) {
+  if (cands.empty()) return 0;
+  auto tm_ = std::chrono::steady_clock::now();
+  std::vector<InfJob> jobs;
+  raw_jobs(cands, jobs);
+  std::vector<InfRes> res;
+  if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, arena_cap, false, fresh_arena, true)) return r;
+  std::vector<Rec> kept;
+  if (int r = raw_accept(h, cands, res, c->recs, kept)) return r;
+  if (int r = splice(c->recs, kept)) return r;
+  TMARK("scan: raw candidates");
+  return 0;
+}
+
+// The stitch buffer holds every candidate's run (atz_scanext.h: at most F + 256 * candidates bytes), plus the 4 KiB
+// of zero slack that d_file has (the kernels read past an end).
 static int stitch_merge(atz_ctx* c, const uint8_t* d_file, uint64_t arena_cap, bool fresh_arena, const StitchPlan& P) {
   if (P.cands.empty()) return 0;
   auto tm_ = std::chrono::steady_clock::now();
   if (int r = c->d_stitch.reserve(P.bytes + 4096)) return r;
   HIPCHK(hipMemsetAsync(c->d_stitch.as<uint8_t>() + P.bytes, 0, 4096, c->st));
   std::vector<Seg> segs;
-  std::vector<InfJob> jobs(P.cands.size());
-  for (size_t k = 0; k < P.cands.size(); k++) {
-    const StitchCand& a = P.cands[k];
-    uint64_t at = a.at;
-    for (uint32_t q = a.p0; q < a.p0 + a.pk; q++) {
-      if (P.len[q]) segs.push_back({SEG_FILE, 0, P.off[q], at, P.len[q]});
-      at += P.len[q];
-    }
-    jobs[k] = {a.at, a.total, ARENA_OUT, ARENA_SLOT};
-  }
+  std::vector<InfJob> jobs;
+  stitch_jobs(P, segs, jobs);
   const double other0 = c->stats.k_other_ms, infl0 = c->stats.k_inflate_ms;
   if (int r = gather_segments(c, d_file, {}, segs, c->d_stitch.as<uint8_t>())) return r;
   std::vector<InfRes> res;
@@ -1651,196 +1451,53 @@ static int stitch_merge(atz_ctx* c, const uint8_t* d_file, uint64_t arena_cap, b
     std::fprintf(stderr, "atz: stitch: %zu candidates, %llu bytes in %zu segments, k_gather %.3f ms, k_inflate %.3f ms\n",
                  P.cands.size(), (unsigned long long)P.bytes, segs.size(), c->stats.k_other_ms - other0,
                  c->stats.k_inflate_ms - infl0);
-  std::vector<Rec> acc;   // (the candidates are in file order and disjoint, as their chains are)
-  for (size_t k = 0; k < P.cands.size(); k++) {
-    const StitchCand& a = P.cands[k];
-    const InfRes& r = res[k];
-    if (r.status != INF_END || r.produced < 1 || r.produced >= (1ull << 31)) continue;
-    if (r.consumed <= P.len[a.p0]) continue;   // ends inside the first chunk: the reference scan's business
-    Rec rec{P.off[a.p0], r.consumed, r.produced, a.type, 0, r.arena_off};
-    rec.noshort = (r.err & INF_HINT_NOSHORT) != 0;
-    rec.mhint = (uint8_t)((r.err >> INF_HINT_MLEV_SHIFT) & 15u);
-    rec.stitch = a.at;
-    rec.p0 = (uint32_t)c->st_off.size();
-    // the pieces the stream touches: the last one ends where the stream does
-    uint64_t sum = 0;
-    for (uint32_t q = a.p0; q < a.p0 + a.pk && sum < r.consumed; q++) {
-      const uint64_t take = std::min<uint64_t>(P.len[q], r.consumed - sum);
-      c->st_off.push_back(P.off[q]); c->st_len.push_back(take);
-      sum += take;
-      rec.pk++;
-    }
-    if (sum != r.consumed) return ATZ_E_INTERNAL;   // (the decoder never reads past the run)
-    // a record made before that meets the hull [offset, offset + hull): the stitched one is dropped
-    if (meets_earlier(c->recs, rec.offset, rec.offset + rec.hull())) {
-      c->st_off.resize(rec.p0); c->st_len.resize(rec.p0);
-      continue;
-    }
-    acc.push_back(rec);
-  }
-  if (int r = splice_records(c, acc)) return r;
+  std::vector<Rec> kept;
+  if (int r = stitch_accept(P, res, c->recs, c->st_off, c->st_len, kept)) return r;
+  if (int r = splice(c->recs, kept)) return r;
   TMARK("scan: stitched candidates");
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Opt-in probe (atz_set_probe).  A raw deflate stream that no zlib header and no container
-// announces: k_probe_ordered tests every byte position of the file for a plausible dynamic-block start, one
-// raw k_inflate launch decodes the survivors that lie in no record made before, and one that decodes to its
-// end with PROBE_MIN_OUT bytes or more and meets no such record becomes a record of type 24 (raw, no hint),
-// which raw_pass walks as it walks a container's body.
-static constexpr uint64_t PROBE_MIN_OUT = 256;   // a dynamic header alone is 40-80 bytes: smaller bodies gain nothing
-static int probe_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, ProbeList& P) {
-  return positions_dev(c, d_file, F, k_probe_ordered, "k_probe_ordered", P);
-}
-
-// The probe's records merged into c->recs (every record made before, complete, in file order): survivors
-// inside a record's hull are not decoded (every byte-aligned block start of a known stream would be one);
-// the rest are decoded to the end of the file (outputs in the scan's arena behind the earlier candidates';
-// fresh_arena: no job ran before), accepted by status and output size, dropped where they meet a record made
-// before, taken greedily in ascending offset.  c->recs keeps its capacity.
 static int probe_merge(atz_ctx* c, const uint8_t* d_file, uint64_t F, uint64_t arena_cap, bool fresh_arena,
                        const ProbeList& P) {
   auto tm_ = std::chrono::steady_clock::now();
-  const std::vector<Rec>& ref = c->recs;
   std::vector<InfJob> jobs;
-  {
-    size_t i = 0;
-    for (const uint64_t p : P.pos) {
-      while (i < ref.size() && ref[i].offset + ref[i].hull() <= p) i++;
-      if (i < ref.size() && ref[i].offset <= p) continue;
-      jobs.push_back({p, F - p, ARENA_OUT, ARENA_SLOT});
-    }
-  }
+  if (int r = probe_jobs(P.pos, F, c->recs, jobs)) return r;
   const double infl0 = c->stats.k_inflate_ms;
   std::vector<InfRes> res;
   if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, arena_cap, false, fresh_arena, true)) return r;
   std::vector<Rec> kept;
   size_t accepted = 0;
-  uint64_t end = 0;
-  for (size_t k = 0; k < jobs.size(); k++) {
-    const InfRes& r = res[k];
-    if (r.status != INF_END || r.produced < PROBE_MIN_OUT || r.produced >= (1ull << 31)) continue;
-    accepted++;
-    const uint64_t lo = jobs[k].in_off, hi = lo + r.consumed;
-    if (meets_earlier(ref, lo, hi)) continue;
-    if (lo < end) continue;   // starts inside the probe record kept before it
-    end = hi;
-    kept.push_back(Rec{lo, r.consumed, r.produced, 24 /* raw, hint none */, 0, r.arena_off});
-  }
+  if (int r = probe_accept(jobs, res, c->recs, kept, accepted)) return r;
   if (timing_on())
     std::fprintf(stderr, "atz: k_probe_ordered: %zu survivors, kernels %.3f ms (both passes), %zu decoded, "
                  "k_inflate %.3f ms, %zu accepted, %zu kept\n", P.pos.size(), P.kernel_ms, jobs.size(),
                  c->stats.k_inflate_ms - infl0, accepted, kept.size());
-  if (int r = splice_records(c, kept)) return r;
+  if (int r = splice(c->recs, kept)) return r;
   TMARK("scan: probe candidates");
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Opt-in segments (atz_set_segments).  deflate(Z_FULL_FLUSH) ends a segment with an empty
-// stored block (its byte-aligned tail is 00 00 FF FF) and starts the next one from a fresh state, so a stream
-// cut by full flushes is a chain of independent raw bodies, each exactly what a one-shot deflate of its bytes
-// writes, but for its end.  k_marker_ordered lists the markers of the file; seg_merge decodes every segment
-// start of the eligible records in one launch of k_inflate's SEG variant and replaces a record whose chain
-// completes by its segments.
-static int markers_dev(atz_ctx* c, const uint8_t* d_file, uint64_t F, MarkerList& M) {
-  return positions_dev(c, d_file, F, k_marker_ordered, "k_marker_ordered", M);
-}
-
-// Eligible: a raw record (type 24-26; its body is the record), or a zlib record whose header says window 15 and
-// that is not stitched (its body lies between the 2 header bytes and the 4 trailer bytes), with a marker q,
-// body_start <= q and q + 4 < body_end.  Jobs: body_start and every such q + 4, each offered the bytes up to
-// body_end, without output (the record's whole decode lies in the arena, or is inflated again).  The chain
-// s_0 = body_start, s_{i+1} = s_i + consumed_i over jobs that ended at a marker with output completes when it
-// reaches a job that ended at a final block exactly at body_end, after at least one marker, with the outputs
-// summing to the record's; then the record is replaced, in place, by Rec{s_i, consumed_i, produced_i, 24 +
-// hint} (a raw parent's hint; a zlib parent's FLEVEL 0, 1 -> fast, 2 -> none, 3 -> max), flags bit 7 on all
-// but the last, and a last segment without output makes no record.  All or nothing.  c->recs keeps its capacity.
-static int seg_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, const MarkerList& M) {
+// (the segments' jobs write no output: a replaced record's decode, in the arena or not, is its segments' side by side)
+static int seg_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64_t F, const MarkerList& M) {
   auto tm_ = std::chrono::steady_clock::now();
-  const std::vector<Rec>& ref = c->recs;
-  struct Elig { size_t rec; uint64_t b0, b1; size_t j0, j1; };
-  std::vector<Elig> el;
+  std::vector<SegElig> el;
   std::vector<InfJob> jobs;
-  for (size_t i = 0; i < ref.size() && !M.pos.empty(); i++) {
-    const Rec& r = ref[i];
-    uint64_t b0 = r.offset, b1 = r.offset + r.comp_len;
-    if (r.type < 24) {
-      if (r.stitch != ~0ull || r.comp_len < 7 || (h[r.offset] >> 4) != 7) continue;
-      b0 += 2; b1 -= 4;
-    } else if (r.type > 26) continue;
-    auto it = std::lower_bound(M.pos.begin(), M.pos.end(), b0);
-    if (it == M.pos.end() || *it + 4 >= b1) continue;
-    Elig e{i, b0, b1, jobs.size(), 0};
-    jobs.push_back({b0, b1 - b0, NO_OUT, 0});
-    for (; it != M.pos.end() && *it + 4 < b1; ++it) jobs.push_back({*it + 4, b1 - (*it + 4), NO_OUT, 0});
-    e.j1 = jobs.size();
-    el.push_back(e);
-  }
+  if (int r = seg_jobs(h, F, c->recs, M.pos, el, jobs)) return r;
   const double infl0 = c->stats.k_inflate_ms;
   std::vector<InfRes> res;
   if (int r = run_inflate_jobs(c, d_file, nullptr, jobs, res, 0, true, true, INF_SEG)) return r;
   std::vector<Rec> merged;
-  merged.reserve(ref.size() + jobs.size());
-  size_t i = 0, chains = 0, made = 0;
-  for (const Elig& e : el) {
-    const Rec& par = ref[e.rec];
-    std::vector<Rec> segs;
-    const int type = par.type >= 24 ? par.type : (h[par.offset + 1] >> 6) == 2 ? 24 : (h[par.offset + 1] >> 6) == 3 ? 26 : 25;
-    uint64_t s = e.b0, sum = 0;
-    size_t k = 0;
-    bool ok = false;
-    for (size_t j = e.j0; j < e.j1;) {
-      const InfRes& r = res[j];
-      if (r.status != INF_END) break;
-      const uint64_t ao = par.arena_off != ~0ull ? par.arena_off + sum : ~0ull;
-      k++;
-      if (r.err & INF_AT_MARKER) {
-        if (r.produced < 1) break;
-        segs.push_back(Rec{s, r.consumed, r.produced, type, 128u, ao});
-        s += r.consumed; sum += r.produced;
-        // the job that starts at s (none: the marker's end is body_end, so no final block follows)
-        j = (size_t)(std::lower_bound(jobs.begin() + j + 1, jobs.begin() + e.j1, s,
-                                      [](const InfJob& x, uint64_t v) { return x.in_off < v; }) - jobs.begin());
-        if (j < e.j1 && jobs[j].in_off != s) break;
-        continue;
-      }
-      if (s + r.consumed != e.b1) break;
-      if (r.produced) segs.push_back(Rec{s, r.consumed, r.produced, type, 0u, ao});
-      sum += r.produced;
-      ok = k >= 2 && sum == par.infl_len;
-      break;
-    }
-    if (!ok) continue;
-    while (i < e.rec) merged.push_back(ref[i++]);
-    i++;   // the parent leaves
-    merged.insert(merged.end(), segs.begin(), segs.end());
-    chains++; made += segs.size();
-  }
-  while (i < ref.size()) merged.push_back(ref[i++]);
+  size_t chains = 0, made = 0;
+  if (int r = seg_accept(h, c->recs, el, jobs, res, merged, chains, made)) return r;
   if (timing_on())
     std::fprintf(stderr, "atz: k_marker_ordered: %zu markers, kernels %.3f ms (both passes), %zu eligible records, "
                  "%zu jobs, k_inflate %.3f ms, %zu chains completed, %zu segments made\n", M.pos.size(), M.kernel_ms,
                  el.size(), jobs.size(), c->stats.k_inflate_ms - infl0, chains, made);
-  if (merged.size() > c->recs.capacity()) return ATZ_E_INTERNAL;
-  if (chains) c->recs.assign(merged.begin(), merged.end());
+  if (chains)
+    if (int r = put_records(c->recs, merged)) return r;
   TMARK("scan: flush segments");
   return 0;
-}
-
-// the last four bytes of record r's stream (its Adler-32 trailer, big-endian) from the host copy h: a
-// stitched record's may straddle its pieces
-static uint32_t rec_trailer(const atz_ctx* c, const Rec& r, const uint8_t* h) {
-  uint32_t t = 0;
-  if (r.stitch == ~0ull) {
-    const uint8_t* e = h + r.offset + r.comp_len;
-    return ((uint32_t)e[-4] << 24) | ((uint32_t)e[-3] << 16) | ((uint32_t)e[-2] << 8) | e[-1];
-  }
-  int got = 0;
-  for (uint32_t q = r.p0 + r.pk; q > r.p0 && got < 4; q--)
-    for (uint64_t b = c->st_len[q - 1]; b > 0 && got < 4; b--, got++) t |= (uint32_t)h[c->st_off[q - 1] + b - 1] << (8 * got);
-  return t;
 }
 
 // where record r's original bytes lie, as an offset from d_file (StreamDev::orig_off, DiffJob::orig_off: the
@@ -1868,8 +1525,8 @@ static int ext_prepare(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint
   c->st_off.clear(); c->st_len.clear();
   std::vector<uint64_t> anchors;
   if (int r = anchors_dev(c, d_file, F, ext_anchor_mask(c), anchors)) return r;   // (no mask: no anchor)
-  raw_candidates(h, F, anchors, E.raw);
-  stitch_candidates(h, anchors, E.stitch);
+  if (int r = raw_candidates(h, F, anchors, E.raw)) return r;
+  if (int r = stitch_candidates(h, F, anchors, E.stitch)) return r;
   if (c->probe_mask)
     if (int r = probe_dev(c, d_file, F, E.probe)) return r;
   if (c->seg_mask)
@@ -1891,7 +1548,7 @@ static int ext_merge(atz_ctx* c, const uint8_t* h, const uint8_t* d_file, uint64
   if (c->probe_mask)
     if (int r = probe_merge(c, d_file, F, S.arena_cap, fresh, E.probe)) return r;
   if (c->seg_mask)
-    if (int r = seg_merge(c, h, d_file, E.marks)) return r;
+    if (int r = seg_merge(c, h, d_file, F, E.marks)) return r;
   return 0;
 }
 
@@ -1999,7 +1656,7 @@ static int inflate_records(atz_ctx* c, const uint8_t* d_file, uint64_t F, size_t
     // Adler-32 of the inflated bytes = the verified trailer (atz_sweep: saved by atz_scan, whose
     // host buffer the caller need not keep alive)
     if (c->recs[s].type >= 24) { c->adler[s] = 0; continue; }   // a raw body has no trailer (TM_RAW trials write none)
-    c->adler[s] = c->hfile ? rec_trailer(c, c->recs[s], c->hfile) : c->scan_trailer[s];
+    c->adler[s] = c->hfile ? rec_trailer(c->recs[s], c->hfile, c->st_off, c->st_len) : c->scan_trailer[s];
   }
   HIPCHK(hipStreamSynchronize(c->st));
   kcollect(c);
@@ -4713,7 +4370,7 @@ int atz_scan(atz_ctx_t* c, const uint8_t* file, uint64_t len, atz_cand_t** out, 
     for (size_t s = 0; s < c->recs.size(); s++) {
       const Rec& r = c->recs[s];
       if (r.comp_len < 4 || r.offset + r.hull() > len) continue;   // atz_sweep reports ATZ_E_REF_UB
-      c->scan_trailer[s] = rec_trailer(c, r, file);
+      c->scan_trailer[s] = rec_trailer(r, file, c->st_off, c->st_len);
     }
     *n = c->recs.size();
     *out = (atz_cand_t*)std::malloc((c->recs.size() + 1) * sizeof(atz_cand_t));

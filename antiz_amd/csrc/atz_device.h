@@ -156,7 +156,8 @@ struct SweepOpts {
 // inside each row of 16 lanes (row_shr 1, 2, 4, 8), then the rows' totals carried by row_bcast:15
 // (into rows 1 and 3) and row_bcast:31 (into rows 2 and 3).  Six VALU adds; no LDS-crossbar
 // permutes, unlike a __shfl_up ladder.  A lane whose DPP source is outside its row (or whose row is
-// masked off) adds the `old` operand, 0.
+// masked off) adds the `old` operand, 0.  (Device code: a host compiler that includes this file skips it.)
+#ifdef __HIPCC__
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
   int x = (int)v;
   x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);   // row_shr:1
@@ -167,5 +168,6 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
   x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31, rows 2 and 3
   return (uint32_t)x;
 }
+#endif
 
 }  // namespace atz

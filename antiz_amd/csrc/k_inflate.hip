@@ -184,6 +184,8 @@ __global__ __launch_bounds__(256) void k_headers_ordered(const uint8_t* __restri
 // Kind 2 (mask bit 2, internal: the stitch extension; atz_container_anchors never passes it):
 // p is the 'I' of a PNG chunk type field "IDAT" whose big-endian length L at p - 4 is below 2^31 and whose
 // payload and CRC lie inside the file, p + 8 + L <= n.
+// The host parsers read a header's bytes on the strength of these length tests: atz_scanext.h states them as the
+// kernel's promises and checks each before it relies on it.
 __device__ inline int anchor_kind(const uint8_t* __restrict__ f, uint64_t p, uint64_t n, uint32_t mask) {
   const uint32_t b0 = f[p];
   if (b0 == 0x50 && (mask & 1u)) {
